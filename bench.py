@@ -1,7 +1,15 @@
 """Benchmark of the Dynamic-plugin hot path on MI355X (BASELINE.json configs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4] [--no-cpu-baseline] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 3|4] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] [--no-extras] ...
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs
+(--dump-outputs) and prints the headline line.  Everything else the line can hold takes runs of
+its own and is measured only with --full: the checks of the timed keys against a stream engine
+and the CPU oracle, one batch's latency, the per-kernel times and rooflines, the matrix /
+selection / cold-cache / greedy / drop-in / controller legs and the CPU baseline (the --no-*
+options switch parts of those off).  --leg runs one leg alone, as before.
 
 Headline (the JSON line's `value`): one step = one scheduling batch of the
 reference's hot path over one node shard, keys-only (chosen node per pod):
@@ -73,11 +81,28 @@ KERNEL_PMC = {
 
 def pmc_name_match(kname, base, args):
     """rocprof's kernel name kname is `base` (with any template arguments) whose arguments at the
-    given positions have the given values."""
-    head = kname.split("(", 1)[0]
-    tmpl = head[head.index("<") + 1:head.rindex(">")].split(", ") if "<" in head else []
-    name = head.split("<", 1)[0]
-    return name == base and all(-len(tmpl) <= i < len(tmpl) and tmpl[i] == v for i, v in args.items())
+    given positions have the given values.  Brackets are matched, not searched for: a summary holds
+    other libraries' kernels too, whose names may be cut inside their template arguments."""
+    name = kname.split("<", 1)[0].split("(", 1)[0]
+    if name != base:
+        return False
+    rest = kname[len(name):]
+    tmpl, depth, cur = [], 1, ""
+    for ch in rest[1:] if rest.startswith("<") else "":
+        if ch in "<(":
+            depth += 1
+        elif ch in ">)":
+            depth -= 1
+        if depth == 0:  # the argument list has closed
+            break
+        if ch == "," and depth == 1:
+            tmpl.append(cur.strip())
+            cur = ""
+        else:
+            cur += ch
+    if cur.strip():
+        tmpl.append(cur.strip())
+    return all(-len(tmpl) <= i < len(tmpl) and tmpl[i] == v for i, v in args.items())
 
 
 def src_hash():
@@ -237,6 +262,12 @@ def parse():
                     help="untimed batches first: two per batch slot, so every slot has anchored its hot-value "
                          "counts (delta form) and sized its scratch before the timed region")
     ap.add_argument("--config", type=int, default=3, choices=(3, 4))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check their keys (stream engine, CPU oracle sample) and measure "
+                         "one batch's latency, the per-kernel times and rooflines, the extra legs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (its keys, and the chosen node and score they "
+                         "pack, one per pod) as DIR/<name>.npy in float64")
     ap.add_argument("--cpu-pods", type=int, default=1920, help="pods in the bounded CPU-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=16, help="upstream kube-scheduler parallelism")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -248,7 +279,8 @@ def parse():
                          "16 x inflight; group: 0 = min(steps, 64))")
     ap.add_argument("--rehearse-collective", action="store_true",
                     help="run the ranks path's N>1 collective on one rank (under torchrun)")
-    ap.add_argument("--no-extras", action="store_true", help="headline step only (matrix / drop-in / controller legs off)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: the matrix / selection / cold / greedy / drop-in / controller legs off")
     ap.add_argument("--leg", default="all", choices=("all", "matrix2", "matrix3", "cold"),
                     help="matrix2 / matrix3 / cold: only that leg (for per-kernel PMC passes)")
     ap.add_argument("--no-cold", action="store_true", help="skip the cold-cache 4M-node K1/K2 roofline leg")
@@ -979,6 +1011,16 @@ def measure_ranks(cd, synth, spec, args, world, rank, local, dev):
         d_keys = d_keys_k[(args.steps - 1) % K]
         keys_agree = all(torch.equal(d_keys, k) for k in d_keys_k) if C == 1 else None
     keys = d_keys.cpu().numpy()
+    m = dict(c=c, N=N, P=P, n_total=n_total, val=val, ts=ts, eng=eng, ms_step=elapsed * 1e3 / args.steps,
+             keys=keys, keys_agree=keys_agree, host=host, K=K, nows=nows, span=span, stream=streams[0],
+             how=("K engines (own copy of the shard's nodes, binding log, scratch) on K HIP streams, batch i on "
+                  "engine i % K; every batch runs the whole step" +
+                  (f"; one RCCL max all-reduce (torch.distributed, one process per GPU) per group of {G} batches' "
+                   f"keys [{G}][P] on its own stream" if coll else "")),
+             engine_path="ranks" + (" (torch.distributed RCCL)" if coll else ""), n_gpus=world)
+    m["close"] = lambda: [e.close() for e in engs]
+    if not args.full:  # a plain run ends with its timed steps
+        return m
     keys_match, keys_match_how = None, "single rank: no combine step"
     if coll:
         if rank == 0:
@@ -1016,15 +1058,8 @@ def measure_ranks(cd, synth, spec, args, world, rank, local, dev):
         e1.record(streams[0])
         torch.cuda.synchronize(dev)
         ar_ms = e0.elapsed_time(e1) / 10
-    m = dict(c=c, N=N, P=P, n_total=n_total, val=val, ts=ts, eng=eng, ms_step=elapsed * 1e3 / args.steps,
-             keys=keys, keys_agree=keys_agree, keys_match=keys_match, keys_match_how=keys_match_how, host=host,
-             batch_latency_ms=batch_latency_ms, kt=kt, ar_ms=ar_ms, K=K, nows=nows, span=span, stream=streams[0],
-             how=("K engines (own copy of the shard's nodes, binding log, scratch) on K HIP streams, batch i on "
-                  "engine i % K; every batch runs the whole step" +
-                  (f"; one RCCL max all-reduce (torch.distributed, one process per GPU) per group of {G} batches' "
-                   f"keys [{G}][P] on its own stream" if coll else "")),
-             engine_path="ranks" + (" (torch.distributed RCCL)" if coll else ""), n_gpus=world)
-    m["close"] = lambda: [e.close() for e in engs]
+    m.update(keys_match=keys_match, keys_match_how=keys_match_how, batch_latency_ms=batch_latency_ms, kt=kt,
+             ar_ms=ar_ms)
     return m
 
 
@@ -1162,6 +1197,27 @@ def measure_group(cd, synth, spec, args, n_dev, dev):
                              for d in range(1, n_dev))
     else:
         keys_agree = None
+    coll = coll_on
+    workers = args.group_threads == 1 or (args.group_threads == -1 and n_dev > 1)
+    m = dict(c=c, N=c.n_nodes, P=P, n_total=n_total, ms_step=elapsed * 1e3 / args.steps,
+             keys=keys, keys_agree=keys_agree, host=host, K=K, nows=nows, span=span,
+             how=(f"one process, crane_dyn_group over {n_dev} device(s) (C ABI, group.cpp): {K} batch slots, each "
+                  "with an engine per device (the slots of a device share one copy of its shard's nodes and log) "
+                  "on its own stream or dispatch queue, batch i on slot i % K; every batch runs the whole shard "
+                  "step on every device" +
+                  (f"; windows of {G} batches (crane_dyn_group_step_keys_batch), then ONE in-place RCCL "
+                   f"ncclAllReduce(int64, max) of a window's keys [{G}][P] per device on a collective stream "
+                   "ordered after the dispatch queues (ncclCommInitAll communicators)" if coll else "") +
+                  ("; enqueued by one worker thread per device" if workers else "; enqueued by the caller's thread") +
+                  ("; the step's kernels written as AQL packets to one user-mode queue per slot (crane_queue: "
+                   "~0.3 us per kernel instead of a HIP launch's 2.6-3.7 us)" if dispatch else
+                   "; the step's kernels launched through HIP on the slots' streams")),
+             engine_path=("group (C ABI, in-library RCCL" + (", rehearsed on one device)" if n_dev == 1 else ")")
+                          if coll else "group (C ABI, one device)") + (", dispatch queues" if dispatch else ""),
+             dispatch_note=dispatch_note, n_gpus=n_dev)
+    m["close"] = lambda: grp.close()
+    if not args.full:  # a plain run ends with its timed steps
+        return m
     # the timed path pinned at full size: the last timed batch and the one before it (another slot,
     # another `now`: the cutoffs moved between them) against one engine over the whole cluster on a
     # HIP stream and against the CPU oracle on a pod sample (checker only, after the timed region)
@@ -1190,8 +1246,6 @@ def measure_group(cd, synth, spec, args, n_dev, dev):
         grp.sync()
     batch_latency_ms = (time.perf_counter() - t1) * 1e3 / nl
     # per-kernel durations: shard 0's engine of slot 0 stepping the same batch on its own stream
-    coll = args.group_collective == 2 or (args.group_collective == 1 and n_dev > 1)
-    workers = args.group_threads == 1 or (args.group_threads == -1 and n_dev > 1)
     eng = grp.engine(0, 0)
     st0 = torch.cuda.Stream(devs[0])
     k0 = torch.empty(P, dtype=torch.int64, device=devs[0])
@@ -1204,24 +1258,8 @@ def measure_group(cd, synth, spec, args, n_dev, dev):
 
     kt = kernel_times(eng, kstep, max(args.steps, 2 * len(nows)))
     val, ts, _ = c.rows(grp.metric_names)
-    m = dict(c=c, N=c.n_nodes, P=P, n_total=n_total, val=val, ts=ts, eng=eng, ms_step=elapsed * 1e3 / args.steps,
-             keys=keys, keys_agree=keys_agree, keys_match=keys_match, keys_match_how=keys_match_how, host=host,
-             pinned=pinned, batch_latency_ms=batch_latency_ms, kt=kt, ar_ms=None, K=K, nows=nows, span=span, stream=st0,
-             how=(f"one process, crane_dyn_group over {n_dev} device(s) (C ABI, group.cpp): {K} batch slots, each "
-                  "with an engine per device (the slots of a device share one copy of its shard's nodes and log) "
-                  "on its own stream or dispatch queue, batch i on slot i % K; every batch runs the whole shard "
-                  "step on every device" +
-                  (f"; windows of {G} batches (crane_dyn_group_step_keys_batch), then ONE in-place RCCL "
-                   f"ncclAllReduce(int64, max) of a window's keys [{G}][P] per device on a collective stream "
-                   "ordered after the dispatch queues (ncclCommInitAll communicators)" if coll else "") +
-                  ("; enqueued by one worker thread per device" if workers else "; enqueued by the caller's thread") +
-                  ("; the step's kernels written as AQL packets to one user-mode queue per slot (crane_queue: "
-                   "~0.3 us per kernel instead of a HIP launch's 2.6-3.7 us)" if dispatch else
-                   "; the step's kernels launched through HIP on the slots' streams")),
-             engine_path=("group (C ABI, in-library RCCL" + (", rehearsed on one device)" if n_dev == 1 else ")")
-                          if coll else "group (C ABI, one device)") + (", dispatch queues" if dispatch else ""),
-             dispatch_note=dispatch_note, n_gpus=n_dev)
-    m["close"] = lambda: grp.close()
+    m.update(val=val, ts=ts, eng=eng, keys_match=keys_match, keys_match_how=keys_match_how, pinned=pinned,
+             batch_latency_ms=batch_latency_ms, kt=kt, ar_ms=None, stream=st0)
     return m
 
 
@@ -1259,7 +1297,7 @@ def main():
     # the drop-in harness runs first, while this process holds no GPU queue (dropin_runs); its
     # snapshot is the config-3 cell measure_group builds (same seeds), checked there
     early = None
-    if (args.leg == "all" and group and args.gpus == 1 and not args.no_extras and not args.no_cpu_baseline
+    if (args.full and args.leg == "all" and group and args.gpus == 1 and not args.no_extras and not args.no_cpu_baseline
             and args.config == 3 and rank == 0):
         cfg = synth.CONFIGS[3]
         c0 = synth.make_cluster(spec, cfg["nodes"], cfg["pods"], n_bindings=cfg["bindings"], seed=20250215 + 3000)
@@ -1296,7 +1334,13 @@ def main():
     else:
         m = measure_ranks(cd, synth, spec, args, world, rank, local, dev)
         n_gpus, solo = world, world == 1
-    finish(cd, synth, spec, args, m, n_gpus, rank, solo, dev, shash)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["keys"])
+    line = headline(synth, args, m, n_gpus, shash)
+    if args.full:
+        finish(cd, synth, spec, args, m, n_gpus, rank, solo, dev, shash, line)
+    elif rank == 0:
+        print(json.dumps(line), flush=True)
     m["close"]()
     if dist.is_initialized():
         if group:
@@ -1304,16 +1348,78 @@ def main():
         dist.destroy_process_group()
 
 
-def finish(cd, synth, spec, args, m, n_gpus, rank, solo, dev, shash):
-    """Rooflines, the extra legs (one GPU) and the JSON line (rank 0)."""
+def dump_outputs(d, keys):
+    """What the last timed step returned, as d/<name>.npy in float64: the packed key of every pod
+    (score << 32 | 0xFFFFFFFF - node, -1 where no node is feasible; below 2^53, so exact) and the
+    chosen node and score it packs (-1 where none).  The inputs are seeded: with the same arguments
+    two builds write comparable files."""
+    os.makedirs(d, exist_ok=True)
+    keys = np.asarray(keys, np.int64)
+    assert np.abs(keys).max(initial=0) < 1 << 53
+    none = keys < 0
+    np.save(os.path.join(d, "keys.npy"), keys.astype(np.float64))
+    np.save(os.path.join(d, "chosen_node.npy"), np.where(none, -1, 0xFFFFFFFF - (keys & 0xFFFFFFFF)).astype(np.float64))
+    np.save(os.path.join(d, "score.npy"), np.where(none, -1, keys >> 32).astype(np.float64))
+
+
+def headline(synth, args, m, n_gpus, shash):
+    """The JSON line of a plain run: the timed steps' figures and what describes them."""
     strong = args.config == 4
-    c, N, P, n_total, val, ts, eng, kt = m["c"], m["N"], m["P"], m["n_total"], m["val"], m["ts"], m["eng"], m["kt"]
+    c, N, P, n_total, ms_step = m["c"], m["N"], m["P"], m["n_total"], m["ms_step"]
+    placements = P / (ms_step / 1e3)
+    return {
+        "metric": "placements/sec",
+        "value": round(placements, 1),
+        "unit": "placements/s",
+        "value_kind": ("pods placed per second, measured: each timed step schedules a batch of "
+                       f"{P} pods (Filter + Score of every pod on every node, hot values from the binding log, "
+                       "the best feasible node per pod); the per-pair rate with every pair's result written to "
+                       "HBM is matrix_config3.evals_per_s (--full)"),
+        "pairs_decided_per_s": round(P * n_total / (ms_step / 1e3), 1),
+        "pairs_decided_note": ("P x nodes_total / step time: every (pod, node) pair's answer is decided exactly, "
+                               "but the step path evaluates a node per pod only where one of its expiries falls "
+                               "inside the batch (DESIGN.md 4.4): a full-rescan equivalent, not an evaluation "
+                               "count; with node shards over N GPUs (weak scaling) it grows with the cluster"),
+        "n_gpus": n_gpus,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "full": bool(args.full),
+        "config": {"workload": (f"config{args.config}: {n_total} nodes ({N} per GPU) x {P} pods, 6 metrics, "
+                                + (f"hot values from one {synth.CONFIGS[4]['bindings']}-entry binding log over "
+                                   "all nodes (each GPU holds its nodes' entries)" if strong else
+                                   f"hot values from a {synth.CONFIGS[3]['bindings']}-entry binding log per "
+                                   "100k-node cell")
+                                + ", README default policy"),
+                   "nodes_total": n_total, "nodes_per_gpu": N, "pods": P, "bindings_gpu0": len(c.b_node),
+                   "parallelism": f"node-shard x{n_gpus}",
+                   "engine": m["engine_path"] + (f" ({m['dispatch_note']})" if m.get("dispatch_note") else ""),
+                   "batches_in_flight": m["K"],
+                   "batch_times": (f"batch i at now0 + (i % {len(m['nows'])}) x {m['span'] / 1e9:g} s (its pods "
+                                   "shifted alike): the hot-value cutoffs move every batch and K2's suffix "
+                                   "search reruns; the cycle bounds the drift of the un-resynced synthetic "
+                                   "snapshot and log")},
+        "batches_in_flight": {"k": m["K"], "how": m["how"], "keys_agree": m["keys_agree"]},
+        "placements_per_s": round(placements, 1),
+        "host": m["host"],
+        "src_hash": shash,
+        "lib_hash": lib_hash(),
+        "chosen_sample": [int(x) for x in m["keys"][:4]],
+    }
+
+
+def finish(cd, synth, spec, args, m, n_gpus, rank, solo, dev, shash, line):
+    """--full: rooflines, the extra legs (one GPU) and the JSON line (rank 0), the plain run's
+    `line` with their fields added."""
+    c, N, P, val, ts, eng, kt = m["c"], m["N"], m["P"], m["val"], m["ts"], m["eng"], m["kt"]
     B = len(c.b_node)
-    ms_step = m["ms_step"]
     stream = m["stream"]
     local = dev.index
-    pairs_per_s = P * n_total / (ms_step / 1e3)
-    placements = P / (ms_step / 1e3)
     now_sync = m["nows"][0]
 
     # Rooflines per kernel (DESIGN.md section 4): ALGORITHMIC bytes per launch / the kernel's
@@ -1473,46 +1579,8 @@ def finish(cd, synth, spec, args, m, n_gpus, rank, solo, dev, shash):
             extras["controller_hot_values"] = controller_leg(cd, O, synth, spec, dev, c, N, B)
 
     if rank == 0:
-        keys = m["keys"]
-        line = {
-            "metric": "placements/sec",
-            "value": round(placements, 1),
-            "unit": "placements/s",
-            "value_kind": ("pods placed per second, measured: each timed step schedules a batch of "
-                           f"{P} pods (Filter + Score of every pod on every node, hot values from the binding log, "
-                           "the best feasible node per pod); the per-pair rate with every pair's result written to "
-                           "HBM is matrix_config3.evals_per_s"),
-            "pairs_decided_per_s": round(pairs_per_s, 1),
-            "pairs_decided_note": ("P x nodes_total / step time: every (pod, node) pair's answer is decided exactly, "
-                                   "but the step path evaluates a node per pod only where one of its expiries falls "
-                                   "inside the batch (DESIGN.md 4.4): a full-rescan equivalent, not an evaluation "
-                                   "count; with node shards over N GPUs (weak scaling) it grows with the cluster"),
-            "n_gpus": n_gpus,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {"workload": (f"config{args.config}: {n_total} nodes ({N} per GPU) x {P} pods, 6 metrics, "
-                                    + (f"hot values from one {synth.CONFIGS[4]['bindings']}-entry binding log over "
-                                       "all nodes (each GPU holds its nodes' entries)" if strong else
-                                       f"hot values from a {synth.CONFIGS[3]['bindings']}-entry binding log per "
-                                       "100k-node cell")
-                                    + ", README default policy"),
-                       "nodes_total": n_total, "nodes_per_gpu": N, "pods": P, "bindings_gpu0": B,
-                       "parallelism": f"node-shard x{n_gpus}",
-                       "engine": m["engine_path"] + (f" ({m['dispatch_note']})" if m.get("dispatch_note") else ""),
-                       "batches_in_flight": m["K"],
-                       "batch_times": (f"batch i at now0 + (i % {len(m['nows'])}) x {m['span'] / 1e9:g} s (its pods "
-                                       "shifted alike): the hot-value cutoffs move every batch and K2's suffix "
-                                       "search reruns; the cycle bounds the drift of the un-resynced synthetic "
-                                       "snapshot and log")},
-            "batches_in_flight": {"k": m["K"], "how": m["how"], "keys_agree": m["keys_agree"],
-                                  "batch_latency_ms": round(m["batch_latency_ms"], 4)},
-            "placements_per_s": round(placements, 1),
+        line["batches_in_flight"]["batch_latency_ms"] = round(m["batch_latency_ms"], 4)
+        line.update({
             "kernel_ms": {k: round(v, 4) for k, v in kt.items()},
             "hot_value_refresh": {
                 "form": "delta" if any(k.startswith("k2_delta") for k in kt) else "recount",
@@ -1523,7 +1591,6 @@ def finish(cd, synth, spec, args, m, n_gpus, rank, solo, dev, shash):
                         "at its now differs from the anchor's and adjusts the anchor counts (kernel_ms, over the timed "
                         "batches' times in turn); re-anchors when they pass half the suffix or the log changes")},
             "allreduce_ms": None if m["ar_ms"] is None else round(m["ar_ms"], 4),
-            "host": m["host"],
             "keys_match_1gpu": m["keys_match"],
             "keys_match_1gpu_how": m["keys_match_how"],
             "keys_match_stream": (all(b["stream"] for b in m["pinned"]) if m.get("pinned") else None),
@@ -1537,13 +1604,10 @@ def finish(cd, synth, spec, args, m, n_gpus, rank, solo, dev, shash):
             "roofline": roofline,
             "roofline_kernels": roofs,
             "roofline_cold": roofline_cold,
-            "src_hash": shash,
-            "lib_hash": lib_hash(),
             "cpu_baseline": cpu,
             "greedy": greedy,
             "host_parse": host_parse,
-            "chosen_sample": [int(x) for x in keys[:4]],
-        }
+        })
         line.update(extras)
         print(json.dumps(line), flush=True)
 

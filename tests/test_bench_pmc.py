@@ -2,6 +2,7 @@
 sources (profiles/pmc/config{3,cold}_<src_hash>.json, tools/gpu_pmc.sh).  These checks run on the
 CPU: when a summary for these sources is committed, every leg's lookup must resolve (a kernel
 renamed by a new template argument once left the line's traffic null without any error)."""
+import glob
 import json
 import os
 import sys
@@ -29,6 +30,24 @@ def test_name_match_template_arguments():
     assert not bench.pmc_name_match("crane::k3s_eval_x", "crane::k3s_eval", {})
     assert bench.pmc_name_match("crane::k3m_matrix<4, 6, 8, false, true, true>", "crane::k3m_matrix",
                                 {-2: "true", -1: "true"})
+    # a summary also holds other libraries' kernels, their names cut inside a template argument
+    cut = ("at::native::reduce_kernel<512, 1, at::native::ReduceOp<bool, at::native::func_wrapper_t<bool, "
+           "at::native::and_kernel_cuda")
+    assert not bench.pmc_name_match(cut, "crane::k3m_matrix", {-2: "true", -1: "true"})
+    assert bench.pmc_name_match("crane::k1_x<4, ns::op<1, 2>, true", "crane::k1_x", {1: "ns::op<1, 2>", -1: "true"})
+
+
+def test_every_committed_summary_can_be_looked_up():
+    """No kernel name in any committed summary makes a lookup raise (a matrix leg's summary with a
+    torch kernel's cut name once ended the bench run after its headline was measured)."""
+    files = sorted(glob.glob(os.path.join(bench.PMC_DIR, "config*.json")))
+    assert files
+    for f in files:
+        pmc = json.load(open(f))
+        for name in bench.KERNEL_PMC:
+            t = bench.pmc_traffic(pmc, name)
+            assert t is None or t >= 0
+        bench.k2_path_traffic(pmc.get("kernels", {}), True, 8_000_000)
 
 
 def test_k2_path_traffic_picks_each_paths_kernels():

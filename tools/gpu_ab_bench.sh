@@ -21,7 +21,7 @@ for rep in 1 2; do
   for v in "$@"; do
     cp crane-scheduler_amd/lib_ab/lib_$v.so $L || exit 1
     for st in 100 20; do
-      timeout -k 10 300 python bench.py --steps $st --warmup 5 --no-extras --no-cpu-baseline $AB_ARGS > $O/b_${v}_${st}_$rep.log 2>&1 || { tail -20 $O/b_${v}_${st}_$rep.log; exit 1; }
+      timeout -k 10 300 python bench.py --full --steps $st --warmup 5 --no-extras --no-cpu-baseline $AB_ARGS > $O/b_${v}_${st}_$rep.log 2>&1 || { tail -20 $O/b_${v}_${st}_$rep.log; exit 1; }
       python3 -c "
 import json; d=json.loads(open('$O/b_${v}_${st}_$rep.log').read().strip().splitlines()[-1])
 print('$v', 'steps $st rep $rep:', d['ms_per_step'], 'ms/batch, one batch', d['batches_in_flight']['batch_latency_ms'], 'kernels', d['kernel_ms'], 'keys', d['keys_match_stream'], d['keys_match_oracle_sample'])"

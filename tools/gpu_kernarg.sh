@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-kernarg}
 mkdir -p $OUT
 run() {  # name, env assignment, bench args...
   local name=$1 envv=$2; shift 2
-  env $envv timeout -k 10 200 python -u bench.py --no-extras --no-cpu-baseline --no-greedy --no-cold "$@" \
+  env $envv timeout -k 10 200 python -u bench.py --full --no-extras --no-cpu-baseline --no-greedy --no-cold "$@" \
     > $OUT/$name.log 2>&1 || { tail -20 $OUT/$name.log; return 1; }
   python3 - $OUT/$name.log "$name" <<'PY'
 import json, sys

@@ -16,7 +16,7 @@ for v in "$@"; do
     echo "$v: $(tail -1 $O/pytest_$v.log)"
   fi
   timeout -k 10 200 python tools/inflight_probe.py --inflight 1,4 > $O/inf_$v.json 2>&1 || { tail $O/inf_$v.json; cp $O/orig.so $L; exit 1; }
-  timeout -k 10 300 python bench.py --config 4 --no-cpu-baseline --no-greedy --no-extras > $O/b4_$v.log 2>&1 || { tail $O/b4_$v.log; cp $O/orig.so $L; exit 1; }
+  timeout -k 10 300 python bench.py --full --config 4 --no-cpu-baseline --no-greedy --no-extras > $O/b4_$v.log 2>&1 || { tail $O/b4_$v.log; cp $O/orig.so $L; exit 1; }
   timeout -k 10 200 python tools/trace_step.py --config 4 > $O/t4_$v.json 2> $O/t4_$v.err || { tail $O/t4_$v.err; cp $O/orig.so $L; exit 1; }
   python3 - "$O" "$v" <<'PY'
 import json, sys

@@ -18,7 +18,7 @@ for rep in 1 2; do
     if [ "$v" != "-" ]; then for o in $v; do case $o in --*) a="$a $o";; *) a="$a --opt $o";; esac; done; fi
     for st in 100 20; do
       f=$O/b_${i}_${st}_$rep.log
-      timeout -k 10 300 python bench.py --steps $st --warmup ${AB_WARMUP:-16} --no-extras --no-cpu-baseline $a $AB_ARGS > $f 2>&1 || { tail -20 $f; exit 1; }
+      timeout -k 10 300 python bench.py --full --steps $st --warmup ${AB_WARMUP:-16} --no-extras --no-cpu-baseline $a $AB_ARGS > $f 2>&1 || { tail -20 $f; exit 1; }
       python3 -c "
 import json; d=json.loads(open('$f').read().strip().splitlines()[-1])
 print('[$v]', 'steps $st rep $rep:', d['ms_per_step'], 'ms/batch, one batch', d['batches_in_flight']['batch_latency_ms'], 'kernels', d['kernel_ms'], 'keys', d['keys_match_stream'], d['keys_match_oracle_sample'])"

@@ -20,7 +20,7 @@ for w in $WL; do
         3m) CMD="python3 $GRAFT_REPO_ROOT/bench.py --leg matrix3 --steps 3";;
         4m) CMD="python3 $GRAFT_REPO_ROOT/tools/stream_bench.py --k2 auto --reps 2";;
         cold) CMD="python3 $GRAFT_REPO_ROOT/bench.py --leg cold --steps 2";;
-        *) CMD="python3 $GRAFT_REPO_ROOT/bench.py --config $w --steps 5 --warmup 1 --inflight 1 --no-cpu-baseline --no-greedy --no-extras";;
+        *) CMD="python3 $PWD/bench.py --full --config $w --steps 5 --warmup 1 --inflight 1 --no-cpu-baseline --no-greedy --no-extras";;
     esac
     for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "valu SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "l2 TCC_HIT_sum TCC_MISS_sum" "lds SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
         set -- $pass

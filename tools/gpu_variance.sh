@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${1:-var}
 mkdir -p $OUT
 for i in $(seq 1 ${2:-3}); do
-  timeout -k 10 300 python -u bench.py --no-cpu-baseline > $OUT/run$i.log 2>&1 || { tail -20 $OUT/run$i.log; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $OUT/run$i.log 2>&1 || { tail -20 $OUT/run$i.log; exit 1; }
   python3 - $OUT/run$i.log $i <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
