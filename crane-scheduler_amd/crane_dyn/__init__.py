@@ -131,6 +131,7 @@ def _load():
         "crane_queue_create": (C.c_int, [C.c_int32, C.c_int32, P(vp)]),
         "crane_queue_wait": (C.c_int, [vp]),
         "crane_queue_last_error": (C.c_char_p, [vp]),
+        "crane_queue_packets": (C.c_uint64, [vp]),
         "crane_queue_destroy": (C.c_int, [vp]),
         "crane_dyn_step_keys_queue": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "crane_dyn_forget_queue": (C.c_int, [vp, vp]),
@@ -168,6 +169,7 @@ ABI_SYMBOLS = (
     "crane_dyn_group_gc_bindings", "crane_dyn_group_binding_count", "crane_dyn_group_refresh_hot_values",
     "crane_dyn_group_hot_values", "crane_dyn_group_node_steps",
     "crane_queue_create", "crane_queue_wait", "crane_queue_last_error", "crane_queue_destroy",
+    "crane_queue_packets",
     "crane_dyn_step_keys_queue", "crane_dyn_forget_queue", "crane_dyn_step_flush",
 )
 
@@ -566,7 +568,9 @@ class Engine:
     def step_keys_queue(self, now_ns, hv_ts_ns, d_now, d_flags, d_keys, queue):
         """step_keys_async with the kernels on a dispatch queue (Queue): the inputs must be complete
         on the device (torch.cuda.synchronize() after writing them); keys after queue.wait() (with
-        engine option step_defer: after the next step on the queue or step_flush(), then the wait)."""
+        engine option step_defer 1 / 2: after the next / the next two steps on the queue, or
+        step_flush(), then the wait; give consecutive steps different key buffers — two in
+        alternation do — or what is pending runs alone first)."""
         P = d_now.numel()
         assert d_keys.numel() == P and d_now.dtype.itemsize == 8 and d_keys.dtype.itemsize == 8
         self._check(lib.crane_dyn_step_keys_queue(self.h, int(now_ns), int(hv_ts_ns), P, C.c_void_p(d_now.data_ptr()),
@@ -574,7 +578,7 @@ class Engine:
                                                   C.c_void_p(d_keys.data_ptr()), queue.h))
 
     def step_flush(self):
-        """Option step_defer: run the last queue step's deferred K3s now (crane_dyn_step_flush)."""
+        """Option step_defer: run what the last queue steps left pending now (crane_dyn_step_flush)."""
         self._check(lib.crane_dyn_step_flush(self.h))
 
     def step_keys_fn(self, d_now, d_flags, d_keys, stream=None):
@@ -705,6 +709,10 @@ class Queue:
             msg = lib.crane_queue_last_error(h).decode() if h.value else ""
             self.close()
             raise CraneError(rc, msg)
+
+    def packets(self):
+        """Dispatch packets (kernel launches) written to the queue so far."""
+        return int(lib.crane_queue_packets(self.h))
 
     def wait(self):
         if lib.crane_queue_wait(self.h):

@@ -317,6 +317,8 @@ hipError_t aql_commit(crane_queue* q) {
 
 uint64_t aql_commits(const crane_queue* q) { return q->commits.load(std::memory_order_acquire); }
 
+uint64_t aql_packets(const crane_queue* q) { return q->next; }
+
 uint64_t aql_completed(const crane_queue* q) {
     // (the signal counts the commits still running; read after the count so a commit between the
     // two reads makes the result smaller, never larger)
@@ -460,6 +462,8 @@ int crane_queue_wait(crane_queue* q) {
 }
 
 const char* crane_queue_last_error(const crane_queue* q) { return aql_error(q); }
+
+uint64_t crane_queue_packets(const crane_queue* q) { return q ? aql_packets(q) : 0; }
 
 int crane_queue_destroy(crane_queue* q) {
     if (!q) return CRANE_OK;

@@ -41,6 +41,7 @@ hipError_t aql_wait(crane_queue* q);
 // after a step without a device-side wait
 uint64_t aql_commits(const crane_queue* q);
 uint64_t aql_completed(const crane_queue* q);
+uint64_t aql_packets(const crane_queue* q);  // dispatch packets written so far
 const char* aql_error(const crane_queue* q);
 // Engines that put steps on a queue register with it (crane_dyn_step_keys_queue), so whichever of
 // the two is destroyed first can tell the other: a queue's destroy hands itself back to every

@@ -136,7 +136,9 @@ struct Options {
     int k2_delta = 1;         // ... and, once anchored, only the bindings whose window rank changed since
                               // the anchor refresh (delta form, HotDelta); 0: every refresh re-counts
     int step_defer = 0;       // 1: a step on a dispatch queue leaves its K3s to the engine's next step,
-                              // which runs it in its first launch (crane_dyn_step_flush; the group sets it)
+                              // which runs it in its first launch (crane_dyn_step_flush; the group sets it);
+                              // 2: it leaves its K1 too, and a step is one launch (kernels.hpp StepOne):
+                              // this batch's K2 + K3p, the previous batch's K1, K3s of the one before
 };
 // Fixed launch shapes (round 6 removed their options; the A/B sweeps that chose them are in
 // profiles/ab/r03_k2_cold_*.txt and profiles/r05/config3_option_sweep_queues.txt)
@@ -211,12 +213,16 @@ struct crane_dyn {
     HotPart hx_g{};
     // delta form (hot_delta_locked): dense anchor counts at suffix starts dl_pos (valid for log
     // version dl_log_ver, N dl_N), the adjustments of the next node pass (zero unless dl_adj_dirty)
-    bool dl_valid = false, dl_pending = false, dl_adj_dirty = true;
+    bool dl_valid = false, dl_pending = false;
+    // two adjustment buffers: a K1 left pending (step_defer 2) still reads one while the next
+    // step's K2 adds to the other; dl_cur: the one of the latest refresh / the next node pass
+    bool dl_adj_dirty[2] = {true, true};
+    int dl_cur = 0;
     bool dl_zero = false;  // this refresh has no binding in any window (K1: adjustments as the anchor)
     uint64_t dl_log_ver = 0;
     int64_t dl_N = -1, dl_B = -1;
     int64_t dl_pos[kMaxWin] = {};
-    DevBuf<uint32_t> dl_base, dl_adj;
+    DevBuf<uint32_t> dl_base, dl_adj[2];
     // binding log on the device: B slots (node < 0 = empty slot)
     int64_t B = 0;
     bool heap_mode = false;
@@ -247,11 +253,13 @@ struct crane_dyn {
     DevBuf<int32_t> mflag, mapos, mtk;
     DevBuf<int64_t> mFs, mIs, mgi;
     DevBuf<unsigned long long> trace;  // [3][kTraceWgs][8] phase stamps (option "trace")
-    DevBuf<int32_t> sperm, scnt;  // K3 step path scratch (step.hip)
-    DevBuf<int64_t> stile, spnow, sbatch;
-    DevBuf<int32_t> sperm2;       // ... the second set of K3p's outputs: steps alternate (sbatch_par)
-    DevBuf<int64_t> stile2, spnow2;
-    int sbatch_par = 0;  // the range of sbatch and the K3p output set the next step uses (StepPlan)
+    // K3 step path scratch (step.hip).  K3p's outputs and the batch ranges of sbatch in three
+    // sets that steps take in turn (sbatch_par: the next step's): with step_defer 2 a launch holds
+    // K3p of one batch, K1 of the one before (reads its tiles and range) and K3s of the one
+    // before that (reads its whole set)
+    DevBuf<int32_t> sperm[3];
+    DevBuf<int64_t> stile[3], spnow[3], sbatch;
+    int sbatch_par = 0;
     // option step_defer: the last step's K3s, not launched yet (its queue, tables, pod set, keys)
     struct PendK3s {
         bool on = false;
@@ -263,17 +271,45 @@ struct crane_dyn {
         const int64_t* tiles = nullptr;
         int64_t P = 0;
         long long* keys = nullptr;
+        int tset = 0;  // the table set stt points into
+        int64_t N = 0;  // the node count it was planned for
     } pend;
+    // step_defer 2: the last step's K1, not launched yet, with its arguments by value (the policy's
+    // window cutoffs, the hot values' stamp, the adjustment buffer: the next step's refresh rewrites
+    // the engine's own), and the K3s that follows it.  pend, when on too, is the batch before
+    struct PendK1 {
+        bool on = false;
+        crane_queue* q = nullptr;
+        K1Args a{};
+        K1Step ks{};
+        PendK3s next;
+        bool reset = false;  // its K3p left the keys' reset to this stage's launch
+        int adj = 0;         // the adjustment buffer it reads and zeroes
+    } pk1;
+    int64_t delta_chunks = 0;    // the delta form's workgroups of the last refresh
+    bool delta_first = false;    // the last refresh launched the delta form (with the step's K3p)
+    bool defer_reset = false;    // this step's keys are what a pending K3s still merges into: if the
+                                 // step goes out as one launch, K3p leaves their reset to the next
+    bool reset_deferred = false; // ... and it did
     DevBuf<int64_t> sel_fth, sel_win, sel_state;  // framework selection (select.hip)
     DevBuf<long long> sel_keys;
     DevBuf<unsigned char> stp_dev;  // node answer tables (crane_dyn_node_steps): bp, ns, ff, score
     HostBuf<unsigned char> stp_host;
-    DevBuf<Mid> smid;
-    DevBuf<Step1> sstep1;
+    // the step tables K1 / K3a write and K3s reads, in two sets: a pending K1 (step_defer 2)
+    // writes one while the K3s beside it reads the other's (set 1 exists only once that form ran)
+    struct TabSet {
+        DevBuf<int32_t> scnt;
+        DevBuf<Mid> smid;
+        DevBuf<Step1> sstep1;
+        DevBuf<int32_t> spm1, ssm0;   // prefix / suffix key maxima of the sorted Step1 records
+        DevBuf<int4> srows;           // per (pod tile, producer block): uniform keys + record ranges
+        DevBuf<int2> sprow;           // ... and middle-piece ranges
+        void release() {
+            scnt.release(); smid.release(); sstep1.release(); spm1.release(); ssm0.release(); srows.release();
+            sprow.release();
+        }
+    } tab[2];
     DevBuf<Step1> sstage;  // K1's one-step staging past its LDS (StepTables::stage)
-    DevBuf<int32_t> spm1, ssm0;   // prefix / suffix key maxima of the sorted Step1 records
-    DevBuf<int4> srows;           // per (pod tile, producer block): uniform keys + record ranges
-    DevBuf<int2> sprow;           // ... and middle-piece ranges
     // caller streams that asynchronous work was enqueued on since the last quiesce: calls that
     // replace engine state (and the synchronous calls on the engine stream) first wait for
     // them — those streams only, not the device (another engine's batches and collectives
@@ -387,7 +423,8 @@ struct Locked {
     // own first launch (option step_defer); every other call runs it first
     explicit Locked(crane_dyn* h, bool keep_pending = false) : g(h->mu), prev(tl_ktimer) {
         tl_ktimer = h->prof ? &h->timer : nullptr;
-        if (!keep_pending && h->pend.on) rc = flush_pending(h);
+        const bool stale = h->sd && (h->sd_node_ver != h->sd->node_ver || h->sd_log_ver != h->sd->log_ver);
+        if ((!keep_pending || stale) && (h->pend.on || h->pk1.on)) rc = flush_pending(h);
         if (!rc && h->sd && (h->sd_node_ver != h->sd->node_ver || h->sd_log_ver != h->sd->log_ver)) rc = adopt(h);
     }
     ~Locked() { tl_ktimer = prev; }
@@ -527,15 +564,29 @@ static int hot_delta_locked(crane_dyn* h, int64_t Bk, const HotCutoffs& pcut, hi
         }
         L = d.start[m];
     }
-    if (h->dl_adj.n < nb) {
-        HIPTRY(h, h->dl_adj.reserve(nb));
-        h->dl_adj_dirty = true;
-    }
-    if (h->dl_adj_dirty) {  // (an earlier refresh's adjustments no node pass consumed, or a new buffer)
-        if (int rc = zero_for(h, h->dl_adj.p, h->dl_adj.n, st)) return rc;
-        h->dl_adj_dirty = false;
+    // (a pending K1 holds one adjustment buffer until its launch: this refresh takes the other)
+    const int ab = h->pk1.on ? h->pk1.adj ^ 1 : h->dl_cur;
+    h->dl_cur = ab;
+    DevBuf<uint32_t>& adj = h->dl_adj[ab];
+    // (step_defer 2: the other buffer too, up front, unless a pending K1 holds it — an allocation
+    // and a fill wait for the queue, and belong to an engine's first step, not its third)
+    for (int b : {ab, ab ^ 1}) {
+        if (b != ab && (h->opt.step_defer != 2 || !tl_aql || h->pk1.on)) break;
+        DevBuf<uint32_t>& x = h->dl_adj[b];
+        if (x.n < nb) {
+            HIPTRY(h, x.reserve(nb));
+            h->dl_adj_dirty[b] = true;
+        }
+        if (h->dl_adj_dirty[b]) {  // (an earlier refresh's adjustments no node pass consumed, or a new buffer)
+            if (int rc = zero_for(h, x.p, x.n, st)) return rc;
+            h->dl_adj_dirty[b] = false;
+        }
     }
     h->dl_zero = false;
+    // every form but the delta launch below: what is pending runs first (the re-anchor rewrites the
+    // anchor a pending K1 reads; that K1 belongs in front of this step's launches in any case)
+    if (h->pk1.on && (Bk == 0 || !anchored || 2 * L > Bk))
+        if (int rc = flush_pending(h)) return rc;
     if (Bk == 0) {
         // no binding inside any window: every count is zero — K1 reads the (clean) adjustments as
         // the anchor too; the anchor itself is kept for the next refresh
@@ -556,20 +607,60 @@ static int hot_delta_locked(crane_dyn* h, int64_t Bk, const HotCutoffs& pcut, hi
         h->dl_B = h->B;
     } else {
         crane_dyn::PendK3s& pk = h->pend;
-        if (pk.on && tl_aql && pk.q == tl_aql && pods && pods->P > 0) {
+        crane_dyn::PendK1& k1 = h->pk1;
+        const bool mine = tl_aql && pods && pods->P > 0;
+        if (k1.on && !(mine && k1.q == tl_aql &&
+                       step_one_workgroups(pk.on ? pk.g.ngroups * pk.g.R : 0, h->N, pods->ntiles, L) <=
+                           (int64_t)kStepOneWgPerCu * h->n_cu)) {
+            // (a launch that is not resident at once — a time jump's many changed bindings —
+            // keeps the launches apart)
+            if (int rc = flush_pending(h)) return rc;
+        }
+        if (k1.on) {
+            // the whole step as one launch (option step_defer 2: step.hip step_one_launch): K3s of the
+            // batch two steps back, the previous batch's K1, this batch's delta form + K3p
+            StepOne s{};
+            s.N = h->N;
+            s.node_offset = h->node_offset;
+            if (pk.on) {
+                s.P_k3s = pk.P;
+                s.keys_k3s = pk.keys;
+                s.st = pk.stt;
+                s.g = pk.g;
+                s.perm = pk.perm;
+                s.pnow = pk.pnow;
+                s.tile_mm = pk.tiles;
+            }
+            s.k1 = &k1.a;
+            s.ks = &k1.ks;
+            s.reset_keys = k1.reset ? k1.next.keys : nullptr;
+            s.reset_P = k1.next.P;
+            s.bnode = h->sd->bnode.p;
+            s.d = &d;
+            s.adj = adj.p;
+            PodPrep pp = *pods;
+            if (h->defer_reset) pp.keys = nullptr;
+            s.pods = &pp;
+            HIPTRY(h, launch_step_one(s, st));
+            h->reset_deferred = h->defer_reset;
+            pk = k1.next;
+            k1.on = false;
+        } else if (pk.on && mine && pk.q == tl_aql) {
             // the previous step's K3s in this launch (option step_defer: step.hip k3s_delta_pods)
             HIPTRY(h, launch_k3s_delta_pods(h->N, h->node_offset, pk.P, pk.keys, pk.stt, pk.g, pk.perm, pk.pnow,
-                                            pk.tiles, h->sd->bnode.p, h->N, d, h->dl_adj.p, *pods, st));
+                                            pk.tiles, h->sd->bnode.p, h->N, d, adj.p, *pods, st));
             pk.on = false;
         } else {
             d.trace = h->trace_region(0);  // (the delta launch stays far below kTraceWgs workgroups at
                                            // config 3; larger ones are not traced)
             if ((pods ? pods->ntiles : 0) + (L + 1023) / 1024 > kTraceWgs) d.trace = nullptr;
-            HIPTRY(h, launch_hot_count_delta(h->sd->bnode.p, h->N, d, h->dl_adj.p, st, pods));
+            HIPTRY(h, launch_hot_count_delta(h->sd->bnode.p, h->N, d, adj.p, st, pods));
         }
         if (pods_done) *pods_done = pods != nullptr && pods->P > 0;
+        h->delta_first = true;
+        h->delta_chunks = (L + 1023) / 1024;
     }
-    h->dl_adj_dirty = true;  // (until the node pass reads and zeroes the adjustments)
+    h->dl_adj_dirty[ab] = true;  // (until the node pass reads and zeroes the adjustments)
     h->dl_pending = true;
     *done = true;
     return CRANE_OK;
@@ -580,6 +671,8 @@ static int hot_delta_locked(crane_dyn* h, int64_t Bk, const HotCutoffs& pcut, hi
 static int hot_values_locked(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, hipStream_t st,
                              const PodPrep* pods = nullptr, bool* pods_done = nullptr) {
     if (pods_done) *pods_done = false;
+    h->delta_first = false;
+    h->reset_deferred = false;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before refreshing hot values");
     DevPolicy& dp = h->dp;
     HotCutoffs cut{};
@@ -646,6 +739,8 @@ static int hot_values_locked(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, hip
         const int rc = hot_delta_locked(h, Bk, pcut, st, pods, pods_done, &done);
         if (rc || done) return rc;
     }
+    if (h->pk1.on)  // (a pending K1 goes in front of any other form's launches)
+        if (int rc = flush_pending(h)) return rc;
     HotPart gx = hot_dedupe_geometry(Bk, h->N, dp.n_win, kK1Block);
     gx.trace = gx.nblk <= kTraceWgs ? h->trace_region(0) : nullptr;
     if (h->opt.k2_form == 0 && gx.ok) {
@@ -702,9 +797,11 @@ static int k1_bs(const crane_dyn* h) {
 // K1 (optionally with the K3 step tables fused in).  Hot values: pending K2
 // counts (consumed), else the values the last consuming pass kept, else the
 // uploaded annotation.
-static int node_pass_locked(crane_dyn* h, hipStream_t st, uint32_t* cnt_out = nullptr, const K1Step* step = nullptr) {
+// Its arguments from the engine's state (*consume: it reads pending K2 counts), and the state
+// after it (k1_launched) — apart, so a step may leave the pass itself to the next launch
+static int k1_args(crane_dyn* h, K1Args& a, uint32_t* cnt_out, const K1Step* step, bool* consume_out) {
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before the node pass");
-    K1Args a{};
+    a = K1Args{};
     a.pol = h->dp;
     a.N = h->N;
     a.val = h->sd->val.p;
@@ -724,8 +821,8 @@ static int node_pass_locked(crane_dyn* h, hipStream_t st, uint32_t* cnt_out = nu
             a.hx_CO = h->k2_sorted.p + g.cap;
             a.hx_nblk = g.nblk;
         } else if (h->dl_pending) {
-            a.buckets = h->dl_adj.p;  // read and zeroed
-            a.bucket_base = h->dl_zero ? h->dl_adj.p : h->dl_base.p;
+            a.buckets = h->dl_adj[h->dl_cur].p;  // read and zeroed
+            a.bucket_base = h->dl_zero ? h->dl_adj[h->dl_cur].p : h->dl_base.p;
             a.buckets_keep = 0;
         } else {
             a.buckets = h->buckets.p;
@@ -741,15 +838,27 @@ static int node_pass_locked(crane_dyn* h, hipStream_t st, uint32_t* cnt_out = nu
     }
     a.threads = k1_bs(h);
     a.trace = (h->N + a.threads - 1) / a.threads <= kTraceWgs ? h->trace_region(1) : nullptr;
-    HIPTRY(h, launch_node_pass(h->shape, a, st, step, h->opt.k1_stream));
+    *consume_out = consume;
+    return CRANE_OK;
+}
+
+static void k1_launched(crane_dyn* h, bool consume, bool keep) {
     if (consume) {
-        if (h->dl_pending) h->dl_adj_dirty = false;  // K1 zeroed the adjustments
+        if (h->dl_pending) h->dl_adj_dirty[h->dl_cur] = false;  // K1 zeroed the adjustments
         else if (!h->hx_pending) h->buckets_zero = !h->buckets_dense;  // K1 zeroed what it read
         h->counts_pending = false;
         h->hx_pending = false;
         h->dl_pending = false;
     }
     h->rec_dirty = !keep;
+}
+
+static int node_pass_locked(crane_dyn* h, hipStream_t st, uint32_t* cnt_out = nullptr, const K1Step* step = nullptr) {
+    K1Args a;
+    bool consume = false;
+    if (int rc = k1_args(h, a, cnt_out, step, &consume)) return rc;
+    HIPTRY(h, launch_node_pass(h->shape, a, st, step, h->opt.k1_stream));
+    k1_launched(h, consume, !step);
     return CRANE_OK;
 }
 
@@ -760,65 +869,69 @@ struct StepPlan {
     bool fuse;  // K3a fused into the node pass (records stale)
     int64_t* batch;       // this step's time range (K3p folds it, K1 reads it)
     int64_t* batch_next;  // the other range: reset by K3p for the next step
-    int32_t* perm;        // this step's K3p outputs (one of two sets, by sbatch_par)
+    int32_t* perm;        // this step's K3p outputs (one of three sets, by sbatch_par)
     int64_t* pnow;
     int64_t* tiles;
+    int tset;             // the table set stt points into
 };
 
 static bool step_path_ok(const crane_dyn* h, int64_t P) {
     return h->opt.keys_path == 0 && h->N >= 0 && h->N < kStepMaxNodes && P < (1LL << 31);
 }
 
-static int step_plan(crane_dyn* h, int64_t P, StepPlan& sp) {
+// tset: the table set (a step that leaves its K1 pending takes the set the pending K3s does not read)
+static int step_plan(crane_dyn* h, int64_t P, StepPlan& sp, int tset = 0) {
     sp.fuse = h->rec_dirty;
+    sp.tset = tset;
+    crane_dyn::TabSet& tb = h->tab[tset];
     const int32_t bs = sp.fuse ? k1_bs(h) : kStepSeg;  // producer workgroup size
     const int32_t nblk = (int32_t)((h->N + bs - 1) / bs);
     sp.g = step_geometry(P, h->N, nblk, 0);
     const StepGeometry& g = sp.g;
-    HIPTRY(h, h->sperm.reserve((size_t)(g.ntiles * 1024)));
-    HIPTRY(h, h->stile.reserve((size_t)(kTileStat * g.ntiles)));
-    HIPTRY(h, h->sperm2.reserve((size_t)(g.ntiles * 1024)));
-    HIPTRY(h, h->stile2.reserve((size_t)(kTileStat * g.ntiles)));
-    HIPTRY(h, h->spnow2.reserve((size_t)(g.ntiles * 1024)));
-    if (!h->sbatch.p) {  // two {tmin, tmax} ranges, alternating between steps, start empty
-        HIPTRY(h, h->sbatch.reserve(4));
+    for (int k = 0; k < 3; ++k) {
+        HIPTRY(h, h->sperm[k].reserve((size_t)(g.ntiles * 1024)));
+        HIPTRY(h, h->stile[k].reserve((size_t)(kTileStat * g.ntiles)));
+        HIPTRY(h, h->spnow[k].reserve((size_t)(g.ntiles * 1024)));
+    }
+    if (!h->sbatch.p) {  // three {tmin, tmax} ranges, taken in turn by the steps, start empty
+        HIPTRY(h, h->sbatch.reserve(6));
         // on the engine stream and waited for: a null-stream copy is not ordered with the
         // non-blocking streams K3p runs on and may land after it (a batch then saw tmin = tmax
         // = 0: every pod scored as at time 0, seen once in test_greedy_then_eval_consistent)
-        static const int64_t empty[4] = {INT64_MAX, INT64_MIN, INT64_MAX, INT64_MIN};
+        static const int64_t empty[6] = {INT64_MAX, INT64_MIN, INT64_MAX, INT64_MIN, INT64_MAX, INT64_MIN};
         HIPTRY(h, hipMemcpyAsync(h->sbatch.p, empty, sizeof(empty), hipMemcpyHostToDevice, h->stream));
         HIPTRY(h, hipStreamSynchronize(h->stream));
         h->sbatch_par = 0;
     }
-    // (the ranges alternate once K3p was launched: pods_ran)
+    // (the ranges move on once K3p was launched: pods_ran.  The range K3p resets for the next step
+    // was last read by the K1 of two steps back, which the previous launch held at the latest)
     sp.batch = h->sbatch.p + 2 * h->sbatch_par;
-    sp.batch_next = h->sbatch.p + 2 * (h->sbatch_par ^ 1);
-    HIPTRY(h, h->spnow.reserve((size_t)(g.ntiles * 1024)));
-    sp.perm = h->sbatch_par ? h->sperm2.p : h->sperm.p;
-    sp.pnow = h->sbatch_par ? h->spnow2.p : h->spnow.p;
-    sp.tiles = h->sbatch_par ? h->stile2.p : h->stile.p;
-    HIPTRY(h, h->scnt.reserve((size_t)std::max<int32_t>(nblk, 1) * 6));  // cnt [nblk][4] + flat [nblk][2]
+    sp.batch_next = h->sbatch.p + 2 * ((h->sbatch_par + 1) % 3);
+    sp.perm = h->sperm[h->sbatch_par].p;
+    sp.pnow = h->spnow[h->sbatch_par].p;
+    sp.tiles = h->stile[h->sbatch_par].p;
+    HIPTRY(h, tb.scnt.reserve((size_t)std::max<int32_t>(nblk, 1) * 6));  // cnt [nblk][4] + flat [nblk][2]
     // per kind and producer block: 2 * bs one-step records, bs * (breakpoints - 1) middle pieces
     const int64_t s1pad = 2 * g.npad, mstride = (int64_t)bs * (step_breakpoints(h->shape) - 1);
     const int64_t mpad = (int64_t)nblk * mstride;
-    HIPTRY(h, h->sstep1.reserve((size_t)(2 * s1pad)));
+    HIPTRY(h, tb.sstep1.reserve((size_t)(2 * s1pad)));
     if (sp.fuse) HIPTRY(h, h->sstage.reserve((size_t)(2 * s1pad)));
-    HIPTRY(h, h->spm1.reserve((size_t)(2 * s1pad)));
-    HIPTRY(h, h->ssm0.reserve((size_t)(2 * s1pad)));
-    HIPTRY(h, h->smid.reserve((size_t)(2 * mpad)));
+    HIPTRY(h, tb.spm1.reserve((size_t)(2 * s1pad)));
+    HIPTRY(h, tb.ssm0.reserve((size_t)(2 * s1pad)));
+    HIPTRY(h, tb.smid.reserve((size_t)(2 * mpad)));
     StepTables& t = sp.stt;
     t = StepTables{};
-    t.cnt = h->scnt.p;
-    t.flat = h->scnt.p + (size_t)nblk * 4;
-    t.single = h->sstep1.p;
+    t.cnt = tb.scnt.p;
+    t.flat = tb.scnt.p + (size_t)nblk * 4;
+    t.single = tb.sstep1.p;
     t.stage = sp.fuse ? h->sstage.p : nullptr;
     t.lds_cap = h->opt.step_lds_cap;
     const bool pieces = h->opt.step_pieces == 1 ||
                         (h->opt.step_pieces == 0 && nblk > 4 * h->n_cu && g.ntiles >= kPieceMinTiles);
     t.piece_work = pieces ? 256 : INT32_MAX;
-    t.pm1 = h->spm1.p;
-    t.sm0 = h->ssm0.p;
-    t.mid = h->smid.p;
+    t.pm1 = tb.spm1.p;
+    t.sm0 = tb.ssm0.p;
+    t.mid = tb.smid.p;
     t.s1pad = s1pad;
     t.mpad = mpad;
     t.bs = bs;
@@ -828,11 +941,11 @@ static int step_plan(crane_dyn* h, int64_t P, StepPlan& sp) {
     t.tiles = sp.tiles;
     const int64_t nrows = g.ntiles * (int64_t)nblk;
     if (h->opt.step_rows && nrows <= kStepRowsMax) {
-        HIPTRY(h, h->srows.reserve((size_t)std::max<int64_t>(nrows, 1)));
-        t.rows = h->srows.p;
+        HIPTRY(h, tb.srows.reserve((size_t)std::max<int64_t>(nrows, 1)));
+        t.rows = tb.srows.p;
         if (pieces) {
-            HIPTRY(h, h->sprow.reserve((size_t)std::max<int64_t>(nrows, 1)));
-            t.prow = h->sprow.p;
+            HIPTRY(h, tb.sprow.reserve((size_t)std::max<int64_t>(nrows, 1)));
+            t.prow = tb.sprow.p;
         }
     }
     t.trace = g.ngroups * g.R <= kTraceWgs ? h->trace_region(2) : nullptr;
@@ -841,7 +954,7 @@ static int step_plan(crane_dyn* h, int64_t P, StepPlan& sp) {
 
 // K3p was launched for a step: the next step folds into the range this one reset
 static void pods_ran(crane_dyn* h, int64_t P) {
-    if (P > 0) h->sbatch_par ^= 1;
+    if (P > 0) h->sbatch_par = (h->sbatch_par + 1) % 3;
 }
 
 static int step_pods(crane_dyn* h, const StepPlan& sp, int64_t P, const int64_t* d_now, const uint8_t* d_flags,
@@ -852,16 +965,47 @@ static int step_pods(crane_dyn* h, const StepPlan& sp, int64_t P, const int64_t*
     return CRANE_OK;
 }
 
+// defer 1: K3s left to the next step's launch (PendK3s); 2: K1 too (PendK1; the caller checked
+// that the streamed pass would run); reset: K3p left the keys' reset to K1's launch
 static int step_rest(crane_dyn* h, const StepPlan& sp, int64_t P, long long* d_keys, hipStream_t st,
-                     bool defer = false) {
+                     int defer = 0, bool reset = false) {
     if (P == 0) return CRANE_OK;
+    crane_dyn::PendK3s nx;
+    nx.on = true;
+    nx.q = tl_aql;
+    nx.stt = sp.stt;
+    nx.g = sp.g;
+    nx.perm = sp.perm;
+    nx.pnow = sp.pnow;
+    nx.tiles = sp.tiles;
+    nx.P = P;
+    nx.keys = d_keys;
+    nx.tset = sp.tset;
+    nx.N = h->N;
     if (sp.fuse) {
         // (the records the fused step leaves stale serve as the streamed pass's scratch)
         const K1Step ks{sp.tiles, sp.batch, (int32_t)sp.g.ntiles, h->dp.noprio, h->dp.wsum, h->dp.winv, sp.stt,
                         h->rec.p, h->opt.k1_tail};
+        if (defer == 2) {
+            // planned now, with the state it would have found and leaves; launched with the next step
+            crane_dyn::PendK1& k1 = h->pk1;
+            bool consume = false;
+            const int adj = h->dl_cur;
+            if (int rc = k1_args(h, k1.a, nullptr, &ks, &consume)) return rc;
+            k1_launched(h, consume, false);
+            k1.on = true;
+            k1.q = tl_aql;
+            k1.ks = ks;
+            k1.next = nx;
+            k1.reset = reset;
+            k1.adj = adj;
+            return CRANE_OK;
+        }
+        if (reset) HIPTRY(h, launch_keys_reset(d_keys, P, st));
         int rc = node_pass_locked(h, st, nullptr, &ks);
         if (rc) return rc;
     } else {
+        if (reset) HIPTRY(h, launch_keys_reset(d_keys, P, st));
         if (h->rec_dirty) {
             int rc = node_pass_locked(h, st);
             if (rc) return rc;
@@ -869,36 +1013,58 @@ static int step_rest(crane_dyn* h, const StepPlan& sp, int64_t P, long long* d_k
         HIPTRY(h, launch_step_nodes(h->shape, h->rec.p, h->N, h->dp.wsum, h->dp.noprio, sp.stt, sp.g, sp.tiles, st));
     }
     if (defer) {  // (the next step's first launch runs it: PendK3s)
-        crane_dyn::PendK3s& pk = h->pend;
-        pk.on = true;
-        pk.q = tl_aql;
-        pk.stt = sp.stt;
-        pk.g = sp.g;
-        pk.perm = sp.perm;
-        pk.pnow = sp.pnow;
-        pk.tiles = sp.tiles;
-        pk.P = P;
-        pk.keys = d_keys;
+        h->pend = nx;
         return CRANE_OK;
     }
     HIPTRY(h, launch_step_pairs(h->shape, h->N, h->node_offset, P, d_keys, sp.stt, sp.g, sp.perm, sp.pnow, sp.tiles, st));
     return CRANE_OK;
 }
 
-// option step_defer: the last step's K3s launched now on its queue (alone) and committed
+// option step_defer: what the last steps left pending, launched now on its queue, in order, and
+// committed: the older batch's K3s (beside the pending K1, when there is one: one launch, which
+// also resets that K1's batch's keys if its K3p left that to it), then that batch's K3s
 namespace {
 int flush_pending(crane_dyn* h) {
     crane_dyn::PendK3s& pk = h->pend;
-    if (!pk.on) return CRANE_OK;
-    pk.on = false;
+    crane_dyn::PendK1& k1 = h->pk1;
+    if (!pk.on && !k1.on) return CRANE_OK;
+    crane_queue* const q = k1.on ? k1.q : pk.q;
     crane_queue* const prev = tl_aql;
-    tl_aql = pk.q;
-    const hipError_t e = launch_step_pairs(h->shape, h->N, h->node_offset, pk.P, pk.keys, pk.stt, pk.g, pk.perm,
-                                           pk.pnow, pk.tiles, h->stream);
-    const hipError_t c = aql_commit(pk.q);
+    tl_aql = q;
+    hipError_t e = hipSuccess;
+    if (k1.on) {
+        if (pk.on || k1.reset) {
+            StepOne s{};
+            s.N = h->N;
+            s.node_offset = h->node_offset;
+            if (pk.on) {
+                s.P_k3s = pk.P;
+                s.keys_k3s = pk.keys;
+                s.st = pk.stt;
+                s.g = pk.g;
+                s.perm = pk.perm;
+                s.pnow = pk.pnow;
+                s.tile_mm = pk.tiles;
+            }
+            s.k1 = &k1.a;
+            s.ks = &k1.ks;
+            s.reset_keys = k1.reset ? k1.next.keys : nullptr;
+            s.reset_P = k1.next.P;
+            e = launch_step_one(s, h->stream);
+        } else {
+            e = launch_node_pass(h->shape, k1.a, h->stream, &k1.ks, 1);
+        }
+        pk = k1.next;
+        k1.on = false;
+    }
+    if (e == hipSuccess && pk.on)
+        e = launch_step_pairs(h->shape, h->N, h->node_offset, pk.P, pk.keys, pk.stt, pk.g, pk.perm, pk.pnow, pk.tiles,
+                              h->stream);
+    pk.on = false;
+    const hipError_t c = aql_commit(q);
     tl_aql = prev;
-    if (e != hipSuccess) return h->hipfail(e, "deferred k3s_eval");
-    if (c != hipSuccess) return h->fail(CRANE_E_HIP, std::string("queue: ") + aql_error(pk.q));
+    if (e != hipSuccess) return h->hipfail(e, "deferred step stages");
+    if (c != hipSuccess) return h->fail(CRANE_E_HIP, std::string("queue: ") + aql_error(q));
     return CRANE_OK;
 }
 }  // namespace
@@ -1008,7 +1174,11 @@ int crane::engine_share_shard(crane_dyn* h, crane_dyn* from) {
 // a queue being destroyed hands itself back (aql.cpp; it has waited for its steps)
 void crane::engine_drop_queue(crane_dyn* h, crane_queue* q) {
     std::lock_guard<std::mutex> g(h->mu);
-    if (h->pend.q == q) h->pend.on = false;  // (a deferred K3s on a queue going away: not run)
+    if ((h->pend.on && h->pend.q == q) || (h->pk1.on && h->pk1.q == q)) {
+        // (stages left pending on a queue going away run now: the engine's state says they did)
+        if (flush_pending(h) == CRANE_OK) (void)aql_wait(q);
+        h->pend.on = h->pk1.on = false;
+    }
     h->busy_q.erase(std::remove(h->busy_q.begin(), h->busy_q.end(), q), h->busy_q.end());
     h->seen_q.erase(std::remove(h->seen_q.begin(), h->seen_q.end(), q), h->seen_q.end());
 }
@@ -1085,9 +1255,11 @@ int crane_dyn_destroy(crane_dyn* h) {
     h->mH.release(); h->mbs.release(); h->mflag.release(); h->mapos.release(); h->mtk.release();
     h->mFs.release(); h->mIs.release(); h->mgi.release();
     h->trace.release();
-    h->sperm2.release(); h->stile2.release(); h->spnow2.release();
-    h->sperm.release(); h->scnt.release(); h->stile.release(); h->sbatch.release(); h->spnow.release(); h->smid.release(); h->sstep1.release(); h->sstage.release();
-    h->spm1.release(); h->ssm0.release(); h->srows.release(); h->sprow.release();
+    for (int k = 0; k < 3; ++k) {
+        h->sperm[k].release(); h->stile[k].release(); h->spnow[k].release();
+    }
+    h->sbatch.release(); h->sstage.release();
+    h->tab[0].release(); h->tab[1].release();
     h->sel_fth.release(); h->sel_win.release(); h->sel_state.release(); h->sel_keys.release();
     h->stp_dev.release(); h->stp_host.release(); h->upd_dev.release(); h->upd_host.release();
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -1117,7 +1289,7 @@ int crane_dyn_step_flush(crane_dyn* h) {
 int crane_dyn_forget_queue(crane_dyn* h, crane_queue* q) {
     if (!h) return CRANE_E_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
-    if (h->pend.on && h->pend.q == q)
+    if ((h->pend.on && h->pend.q == q) || (h->pk1.on && h->pk1.q == q))
         if (int rc = flush_pending(h)) return rc;
     auto sq = std::find(h->seen_q.begin(), h->seen_q.end(), q);
     if (sq != h->seen_q.end()) {
@@ -1153,7 +1325,7 @@ int crane_dyn_set_option(crane_dyn* h, const char* name, int64_t value) {
     else if (n == "step_lds_cap" && value >= 0) o.step_lds_cap = (int)std::min<int64_t>(value, 1 << 30);
     else if (n == "k2_sorted" && range(0, 1)) o.k2_sorted = (int)value;
     else if (n == "k2_delta" && range(0, 1)) o.k2_delta = (int)value;
-    else if (n == "step_defer" && range(0, 1)) o.step_defer = (int)value;
+    else if (n == "step_defer" && range(0, 2)) o.step_defer = (int)value;
     else if (n == "k1_stream" && range(0, 1)) o.k1_stream = (int)value;
     else if (n == "k1_tail" && (value == 0 || value == 1 || value == 4)) o.k1_tail = (int)value;
     else if (n == "trace" && range(0, 1)) {
@@ -1566,21 +1738,59 @@ int crane_dyn_step_keys_queue(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, in
     int rc = CRANE_OK;
     {
         OnQueue on(q);
-        const bool defer = h->opt.step_defer != 0;
-        // a deferred K3s of another queue, or one writing the keys this step writes (its K3p resets
-        // them), runs first, alone
-        if (h->pend.on && (h->pend.q != q || h->pend.keys == keys || !defer)) rc = flush_pending(h);
+        const int defer = h->opt.step_defer;
+        crane_dyn::PendK3s& pk = h->pend;
+        crane_dyn::PendK1& k1 = h->pk1;
+        // What is pending runs first, alone: stages of another queue; a K3s writing the keys this
+        // step writes (its K3p resets them) unless a pending K1 follows it (then this step, as
+        // one launch, leaves the reset to the next: two buffers in alternation never drain); the
+        // same keys on consecutive steps; stages planned for another batch size or node count (the
+        // plan below may reallocate buffers they point into)
+        h->defer_reset = false;
+        if (pk.on || k1.on) {
+            crane_queue* const pq = k1.on ? k1.q : pk.q;
+            const int64_t pP = k1.on ? k1.next.P : pk.P;
+            const int64_t pN = k1.on ? k1.next.N : pk.N;
+            bool drain = pq != q || !defer || pP != P || pN != h->N || (pk.on && pk.P != P);
+            if (k1.on) drain = drain || k1.next.keys == keys;
+            else drain = drain || pk.keys == keys;
+            if (drain) rc = flush_pending(h);
+            else h->defer_reset = k1.on && pk.on && pk.keys == keys;
+        }
         h->rec_dirty = true;
         StepPlan sp{};
-        if (!rc) rc = step_plan(h, P, sp);
+        // (the table set a pending stage does not hold: its K3s reads it after this step's K1 is planned)
+        const int tset = k1.on ? k1.next.tset ^ 1 : pk.on ? pk.tset ^ 1 : 0;
+        // (both table sets from the first step on, where the one-launch form can apply at all:
+        // an allocation waits for the device)
+        if (!rc && defer == 2 && !k1.on && !pk.on && step_one_has(h->shape) && h->opt.k1_stream &&
+            (h->N + kK1Block - 1) / kK1Block <= (int64_t)kStepOneWgPerCu * h->n_cu)
+            rc = step_plan(h, P, sp, 1);
+        if (!rc) rc = step_plan(h, P, sp, defer == 2 ? tset : 0);
         const PodPrep pp{d_now, d_flags, P, sp.g.ntiles, sp.perm, sp.pnow, sp.tiles, keys, sp.batch, sp.batch_next};
         bool pods_done = false;
         if (!rc) rc = hot_values_locked(h, now_ns, hv_ts_ns, h->stream, &pp, &pods_done);
         if (pods_done) pods_ran(h, P);
+        const bool reset = h->reset_deferred;
+        h->defer_reset = h->reset_deferred = false;
         // (not taken into the first launch: before this step's node pass rewrites its tables)
-        if (!rc && h->pend.on) rc = flush_pending(h);
+        if (!rc && (pk.on || k1.on) && !(h->delta_first && pk.on && !k1.on && pk.tset != sp.tset))
+            rc = flush_pending(h);
         if (!rc && !pods_done) rc = step_pods(h, sp, P, d_now, d_flags, keys, h->stream);
-        if (!rc) rc = step_rest(h, sp, P, keys, h->stream, defer);
+        // step_defer 2 leaves K1 to the next launch when this step's first launch was the delta
+        // form's with K3p, the streamed 4 x 6 pass would run, and the one launch of a steady
+        // state (K3s + K1 + K3p + as many delta chunks as now) is resident at once; else as 1
+        int dl = defer;
+        if (defer == 2) {
+            const bool stream_k1 = h->opt.k1_stream && sp.fuse && !h->hx_pending && k1_bs(h) == kK1Block &&
+                                   step_one_has(h->shape) && h->N > 0;
+            const bool fits = step_one_workgroups(sp.g.ngroups * sp.g.R, h->N, sp.g.ntiles, 0) + h->delta_chunks <=
+                              (int64_t)kStepOneWgPerCu * h->n_cu;
+            if (!(h->delta_first && pods_done && !h->dl_zero && stream_k1 && fits)) dl = 1;
+        }
+        // (a K3s still pending goes in front of a K1 launched now and of the K3s pending after it)
+        if (!rc && dl != 2 && pk.on) rc = flush_pending(h);
+        if (!rc) rc = step_rest(h, sp, P, keys, h->stream, dl, reset);
     }
     // (what was written runs even after an error: the packets before it are whole)
     const hipError_t ce = aql_commit(q);

@@ -117,7 +117,8 @@ struct crane_dyn_group {
     // (crane_dyn_group_step_keys_async / _schedule with the collective on: RCCL follows each batch
     // on its stream).  ring_kind of their kernargs
     int dispatch = -1, ring_kind = 0;
-    int defer = 1;  // engine option step_defer on the queues' engines (a step's K3s in the slot's next launch)
+    int defer = 2;  // engine option step_defer on the queues' engines (2: a slot's step is one launch, with the
+                    // K1 of its previous batch and the K3s of the one before; 1: only K3s rides in the next launch)
     std::vector<std::vector<crane_queue*>> q;  // [slot][shard]
     bool comm_broken = false;
     uint64_t batch = 0;
@@ -692,7 +693,7 @@ int ensure_queues(crane_dyn_group* g, bool* qmode) {
                 return g->fail(CRANE_E_HIP, m);
             }
             g->q[(size_t)s][(size_t)i] = qq;
-            // the slot's K3s rides in its next step's first launch (flushed at wait_all)
+            // the slot's K3s (and K1) ride in its next steps' launches (flushed at wait_all)
             if (g->eng[(size_t)s][(size_t)i])
                 (void)crane_dyn_set_option(g->eng[(size_t)s][(size_t)i], "step_defer", g->defer);
         }
@@ -903,7 +904,7 @@ int crane_dyn_group_set_option(crane_dyn_group* g, const char* name, int64_t val
     if (g->n <= 0) return g->fail(CRANE_E_STATE, "group was not created successfully");
     const std::string nm = name;
     if (nm == "defer") {
-        if (value < 0 || value > 1) return g->fail(CRANE_E_INVALID, "defer: 0 | 1");
+        if (value < 0 || value > 2) return g->fail(CRANE_E_INVALID, "defer: 0 | 1 | 2");
         if (wait_all(g)) return CRANE_E_STATE;
         g->defer = (int)value;
         for (auto& row : g->eng)

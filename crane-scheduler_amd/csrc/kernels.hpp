@@ -58,13 +58,14 @@ inline hipError_t klaunch(const char* name, void (*kernel)(KArgs...), dim3 grid,
 // load -> wait -> branch, the policy words under per-term conditions) hit the scalar cache instead
 // of each waiting for its own L2 round trip.  Called after a kernel's first vector loads are
 // issued, so the wait overlaps theirs.
-template <int BYTES>
+// (FROM: the lines from that byte on, for a body whose arguments lie behind another's.)
+template <int BYTES, int FROM = 0>
 __device__ __forceinline__ void kernarg_warm() {
     typedef const uint32_t __attribute__((address_space(4)))* kptr;
     const kptr p = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
     uint32_t x = 0;
 #pragma unroll
-    for (int i = 0; i < BYTES / 4; i += 16) x ^= p[i];
+    for (int i = FROM / 64 * 16; i < BYTES / 4; i += 16) x ^= p[i];
     asm volatile("" ::"s"(x));
 }
 
@@ -227,7 +228,7 @@ struct PodPrep {
     int32_t* perm;
     int64_t* pnow;
     int64_t* tile_mm;
-    long long* keys;
+    long long* keys;        // reset to -1, or null (the one-launch queue step resets them a launch later)
     // the batch's time range {tmin, tmax}: every tile folds its pods' range in with one relaxed
     // atomic min / max (no tile waits for another), or null.  batch_next: the other of the two
     // ranges the engine alternates between batches, reset to {INT64_MAX, INT64_MIN} by tile 0 for
@@ -338,6 +339,46 @@ hipError_t launch_k3s_delta_pods(int64_t N_k3s, int64_t node_offset, int64_t P_k
                                  const StepTables& st, const StepGeometry& g, const int32_t* perm, const int64_t* pnow,
                                  const int64_t* tile_mm, const int32_t* bnode, int64_t N, const HotDelta& d,
                                  uint32_t* adj, const PodPrep& pods, hipStream_t s);
+struct K1Args;
+struct K1Step;
+// One step on a dispatch queue as one launch (step.hip step_one_launch): K3s of the batch two
+// steps back, the streamed K1 of the previous batch and this batch's delta-form K2 + K3p, side
+// by side.  The three work on different batches and share nothing within the launch: K3s reads
+// the tables and pod set K1 and K3p wrote two and one launches ago (the engine keeps two sets of
+// tables, three of pod sets, two of adjustments), and the keys K3s merges into are reset beside
+// the K1 of their own batch (reset_keys), one launch before.  Any part may be absent (P_k3s = 0,
+// k1 null, d null).  Instances: the 4 x 6 record shape (step_one_has).
+struct StepOne {
+    int64_t N, node_offset;
+    // K3s (launch_step_pairs' arguments)
+    int64_t P_k3s;
+    long long* keys_k3s;
+    StepTables st;
+    StepGeometry g;
+    const int32_t* perm;
+    const int64_t* pnow;
+    const int64_t* tile_mm;
+    // K1 (launch_stream_steps' arguments), and the keys its batch's K3s will merge into, reset
+    // to -1 here (null: K3p did)
+    const K1Args* k1;
+    const K1Step* ks;
+    long long* reset_keys;
+    int64_t reset_P;
+    // the delta form + K3p (launch_hot_count_delta's arguments)
+    const int32_t* bnode;
+    const HotDelta* d;
+    uint32_t* adj;
+    const PodPrep* pods;
+};
+bool step_one_has(int shape);
+// workgroups of such a launch, and how many of them a compute unit holds at once (from the
+// kernel's LDS union and its 512-lane workgroups at <= 72 VGPRs): the engine takes the form only
+// when the whole launch is resident (every body's span is then one workgroup's chain)
+int64_t step_one_workgroups(int64_t nk3s, int64_t N_k1, int64_t ntiles, int64_t delta_len);
+extern const int kStepOneWgPerCu;
+hipError_t launch_step_one(const StepOne& s, hipStream_t st);
+// keys[0..P) = -1 (a step whose K3p left the reset to a later launch that then did not happen)
+hipError_t launch_keys_reset(long long* keys, int64_t P, hipStream_t st);
 // K3p: perm, pnow [ntiles * 1024], tile_mm [kTileStat * ntiles]; initialises keys[0..P) to -1
 hipError_t launch_step_pods(const int64_t* now, const uint8_t* flags, int64_t P, long long* keys, int64_t* batch,
                             int64_t* batch_next,

@@ -44,7 +44,7 @@ __device__ __forceinline__ void k3p_tile(const int64_t t, const PodPrep& pp, uns
         ds[u] = live[u] && pp.flags && (pp.flags[p] & 1u);
         tn[u] = live[u] ? pp.now[p] : 0;
         if (p + 1 < pend) inorder &= tn[u] <= pp.now[p + 1];
-        if (live[u]) pp.keys[p] = -1;
+        if (live[u] && pp.keys) pp.keys[p] = -1;  // (null: reset elsewhere, the one-launch queue step)
     }
     int32_t e0, e1;  // kind boundaries: first slot of class >= 1 and of class 2 (pod counts per kind)
     if (__syncthreads_and(inorder)) {

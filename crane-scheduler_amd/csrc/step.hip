@@ -37,6 +37,7 @@
 #include "pods.hpp"
 #include "lds_hash.hpp"
 #include "step_node.hpp"
+#include "k1stream_body.hpp"
 
 #ifndef K3S_BUCKETS  // slot searches through a per-kind time-bucket table (A/B: 0 plain binary search)
 #define K3S_BUCKETS 1
@@ -189,26 +190,42 @@ __device__ __forceinline__ void tree_max(int32_t* tree, int32_t a, int32_t b, in
     }
 }
 
-__device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, const int32_t* __restrict__ perm,
-                                         const int64_t* __restrict__ pnow, const int64_t* __restrict__ tile_mm,
-                                         int64_t P, int64_t node_offset, int32_t R, long long* __restrict__ keys) {
-    __shared__ int64_t tt[kK3sPods];         // the tile's pod times (sorted per kind)
-    __shared__ int32_t tree[2 * kK3sPods];   // range maxima: node i covers its leaves' slots
-    __shared__ int32_t umax[2];
+// K3s's LDS (one workgroup): its own kernels hold one statically, the one-launch step carves it
+// from the launch's union (step_one_launch)
+struct K3sLds {
+    int64_t tt[kK3sPods];         // the tile's pod times (sorted per kind)
+    int32_t tree[2 * kK3sPods];   // range maxima: node i covers its leaves' slots
+    int32_t umax[2];
     // work lists (slices of <= kK3sListBlk blocks): records stepping inside / middle pieces per
     // (block, kind), turned in place into their exclusive prefix (+ the total); the first record
     // stepping inside per (block, kind).  Small: K3s runs several rounds of workgroups at config 4
     // and its LDS sets how many share a CU
-    __shared__ int32_t wpre[4 * kK3sListBlk + 1];
-    __shared__ int32_t wjl[2 * kK3sListBlk];
-    __shared__ int32_t wpl[2 * kK3sListBlk];  // the first middle piece per (block, kind)
+    int32_t wpre[4 * kK3sListBlk + 1];
+    int32_t wjl[2 * kK3sListBlk];
+    int32_t wpl[2 * kK3sListBlk];  // the first middle piece per (block, kind)
     // item -> its entry: the list's records and pieces expanded (one LDS read per item instead of a
     // binary search of the prefix, 8 dependent reads)
-    __shared__ uint8_t imap[kK3sRecList + kK3sPieceList];
+    uint8_t imap[kK3sRecList + kK3sPieceList];
 #if K3S_BUCKETS
     // per kind, the first slot of each time bucket (bucket k: [lo + k 2^sh, lo + (k + 1) 2^sh)): a
     // slot search reads its bucket's two bounds and searches the few slots between them
-    __shared__ int32_t sfirst[2][kSearchBuckets + 1];
+    int32_t sfirst[2][kSearchBuckets + 1];
+#endif
+};
+
+__device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, const int32_t* __restrict__ perm,
+                                         const int64_t* __restrict__ pnow, const int64_t* __restrict__ tile_mm,
+                                         int64_t P, int64_t node_offset, int32_t R, long long* __restrict__ keys,
+                                         K3sLds& lds) {
+    int64_t* const tt = lds.tt;
+    int32_t* const tree = lds.tree;
+    int32_t* const umax = lds.umax;
+    int32_t* const wpre = lds.wpre;
+    int32_t* const wjl = lds.wjl;
+    int32_t* const wpl = lds.wpl;
+    uint8_t* const imap = lds.imap;
+#if K3S_BUCKETS
+    int32_t(*const sfirst)[kSearchBuckets + 1] = lds.sfirst;
 #endif
     CRANE_TSTAMP(st.trace, b, 0);
     const int32_t r = (int32_t)(b % R);
@@ -542,7 +559,8 @@ __global__ __launch_bounds__(kK3sThreads) void k3s_eval(StepTables st, const int
 #if K3_KWARM
     kernarg_warm<(int)sizeof(StepTables) + 64>();
 #endif
-    k3s_body((int64_t)blockIdx.x, st, perm, pnow, tile_mm, P, node_offset, R, keys);
+    __shared__ K3sLds lds;
+    k3s_body((int64_t)blockIdx.x, st, perm, pnow, tile_mm, P, node_offset, R, keys, lds);
 }
 
 // The previous step's K3s and this step's first launch (the delta form's K2 + K3p's pod tiles)
@@ -571,12 +589,79 @@ __global__ __launch_bounds__(kK3sThreads) void k3s_delta_pods(K3sArgs k, int32_t
 #endif
     const int64_t b = blockIdx.x;
     if (b < nk3s) {
-        k3s_body(b, k.st, k.perm, k.pnow, k.tile_mm, k.P, k.node_offset, k.R, k.keys);
+        __shared__ K3sLds lds;
+        k3s_body(b, k.st, k.perm, k.pnow, k.tile_mm, k.P, k.node_offset, k.R, k.keys, lds);
         return;
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
     if (b - nk3s < pp.ntiles) k3p_tile<kK3sThreads>(b - nk3s, pp, dyn_lds);
     else k2_delta_body<kK3sThreads>((int32_t)(b - nk3s - pp.ntiles), bnode, N, d, adj);
+}
+
+// ---------------------------------------------------------------- one launch per queue step
+// (kernels.hpp StepOne.)  Workgroups by blockIdx: K3s's first (nk3s = ngroups * R is a multiple
+// of 8 whenever nblk >= 8, so its XCD placement is its own launch's), then K1's blocks padded to
+// a multiple of 8 (K1 is fed its local index and count: block -> XCD as in its own launch, which
+// K3s's XCD groups rely on), then the pod tiles, then the delta form's chunks.  Workgroups are
+// 512 lanes; K1's body is 256: waves 4-7 of a K1 workgroup reset their slice of the keys and
+// return before the body's first barrier (a barrier waits only for the waves still running).
+// The bodies' LDS is one union carved from the dynamic segment.
+struct KeyReset {
+    long long* keys;
+    int64_t P;
+};
+constexpr size_t kDeltaLds = sizeof(uint32_t) * 2 * (size_t)kDeltaSlots + sizeof(uint16_t) * kDeltaMaxWin * kDeltaChunk;
+constexpr size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
+constexpr size_t kStepOneLds = cmax(cmax(sizeof(K1Lds<4, 6>), sizeof(K3sLds)), cmax(kK3pLds, kDeltaLds));
+static_assert(kStepOneLds >= sizeof(K1Lds<4, 6>) && kStepOneLds >= sizeof(K3sLds) && kStepOneLds >= kK3pLds &&
+                  kStepOneLds >= kDeltaLds,
+              "the union holds the largest body");
+static_assert(kStepOneLds + 512 <= 53 * 1024, "three workgroups per compute unit (160 KiB)");
+// resident workgroups per compute unit: LDS (+ the bodies' few static words), and 8-wave
+// workgroups at 7 waves per SIMD
+const int kStepOneWgPerCu = (int)std::min<size_t>(160 * 1024 / (kStepOneLds + 512), 4 * (K1S_WAVES - 1) / kK3sWaves);
+// kernarg offsets (each argument at its natural alignment): K3sArgs, three counts, KeyReset, K1's
+constexpr int kOneK3sEnd = (int)sizeof(K3sArgs) + 16;
+constexpr int kOneK1End = kOneK3sEnd + (int)sizeof(KeyReset) + (int)sizeof(K1Args) + (int)sizeof(K1Step) + 8;
+constexpr int kOneEnd = kOneK1End + 16 + (int)sizeof(HotDelta) + 8 + (int)sizeof(PodPrep);
+
+template <bool FULL>
+// (the instance for any 4 x 6 policy needs 73 registers: built for 6 waves per SIMD, which holds
+// the same three 8-wave workgroups per compute unit)
+__global__ __launch_bounds__(kK3sThreads) __attribute__((amdgpu_waves_per_eu(FULL ? K1S_WAVES : K1S_WAVES - 1)))
+void step_one_launch(K3sArgs k, int32_t nk3s, int32_t nk1, int32_t nk1pad, KeyReset kr, K1Args a, K1Step step,
+                     const int32_t* __restrict__ bnode, int64_t N, HotDelta d, uint32_t* __restrict__ adj, PodPrep pp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
+    int64_t b = blockIdx.x;
+    if (b < nk3s) {
+#if K3_KWARM
+        kernarg_warm<kOneK3sEnd>();
+#endif
+        k3s_body(b, k.st, k.perm, k.pnow, k.tile_mm, k.P, k.node_offset, k.R, k.keys,
+                 *reinterpret_cast<K3sLds*>(dyn_lds));
+        return;
+    }
+    b -= nk3s;
+    if (b < nk1pad) {
+        if (b >= nk1) return;
+        if (threadIdx.x >= 256) {
+            for (int64_t p = b * 256 + (threadIdx.x - 256); p < kr.P; p += (int64_t)nk1 * 256) kr.keys[p] = -1;
+            return;
+        }
+        k1_stream_body<4, 6, FULL, kOneK1End>(a, step, b, nk1, *reinterpret_cast<K1Lds<4, 6>*>(dyn_lds));
+        return;
+    }
+    b -= nk1pad;
+#if K3_KWARM
+    kernarg_warm<kOneEnd, kOneK1End>();
+#endif
+    if (b < pp.ntiles) k3p_tile<kK3sThreads>(b, pp, dyn_lds);
+    else k2_delta_body<kK3sThreads>((int32_t)(b - pp.ntiles), bnode, N, d, adj);
+}
+
+__global__ __launch_bounds__(256) void keys_reset(long long* __restrict__ keys, int64_t P) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p < P) keys[p] = -1;
 }
 
 StepGeometry step_geometry(int64_t P, int64_t N, int32_t nblk, int32_t blk_per_wg) {
@@ -651,6 +736,51 @@ hipError_t launch_k3s_delta_pods(int64_t N_k3s, int64_t node_offset, int64_t P_k
     const K3sArgs k{st, perm, pnow, tile_mm, P_k3s, node_offset, g.R, keys_k3s};
     return klaunch("k3s_eval+k2_delta+k3p_pods", k3s_delta_pods, dim3((unsigned)grid), dim3(kK3sThreads), lds, s, k,
                    (int32_t)nk, bnode, N, d, adj, pp);
+}
+
+bool step_one_has(int shape) { return shape == kShape4x6; }
+
+int64_t step_one_workgroups(int64_t nk3s, int64_t N_k1, int64_t ntiles, int64_t delta_len) {
+    const int64_t nk1 = (N_k1 + 255) / 256;
+    return nk3s + (nk1 + 7) / 8 * 8 + ntiles + (delta_len + kDeltaChunk - 1) / kDeltaChunk;
+}
+
+hipError_t launch_step_one(const StepOne& s, hipStream_t st) {
+    const bool k3s = s.P_k3s > 0 && s.N > 0, k1 = s.k1 && s.ks && s.k1->N > 0;
+    const bool delta = s.d != nullptr, pods = s.pods && s.pods->P > 0;
+    if (delta && (s.d->n_win < 1 || s.d->n_win > kDeltaMaxWin || s.d->n_rng < 0 || s.d->n_rng > kMaxWin ||
+                  s.N >= (1LL << 27)))
+        return hipErrorInvalidValue;
+    if (k1 && (s.k1->threads != 256 || s.k1->out || s.k1->hx_region || !s.ks->st.stage)) return hipErrorInvalidValue;
+    const int64_t nk = k3s ? s.g.ngroups * s.g.R : 0;
+    const int64_t nk1 = k1 ? (s.k1->N + 255) / 256 : 0, nk1pad = (nk1 + 7) / 8 * 8;
+    const int64_t L = delta && s.d->n_rng > 0 ? s.d->start[s.d->n_rng] : 0;
+    const int64_t grid = nk + nk1pad + (pods ? s.pods->ntiles : 0) + (L + kDeltaChunk - 1) / kDeltaChunk;
+    if (grid >= (1LL << 31)) return hipErrorInvalidValue;
+    if (grid == 0) return hipSuccess;
+    const K3sArgs k{s.st, s.perm, s.pnow, s.tile_mm, k3s ? s.P_k3s : 0, s.node_offset, s.g.R, s.keys_k3s};
+    const KeyReset kr{s.reset_keys, k1 && s.reset_keys ? s.reset_P : 0};
+    const K1Args a = k1 ? *s.k1 : K1Args{};
+    const K1Step ks = k1 ? *s.ks : K1Step{};
+    const HotDelta d = delta ? *s.d : HotDelta{};
+    const PodPrep pp = pods ? *s.pods : PodPrep{};
+    const bool full = K1S_FULL && k1 && a.pol.npd == 4 && a.pol.npr == 6 && a.pol.n_win == kFullWin;
+    static const hipError_t attr[2] = {
+        hipFuncSetAttribute((const void*)step_one_launch<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kStepOneLds),
+        hipFuncSetAttribute((const void*)step_one_launch<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)kStepOneLds)};
+    if (attr[full] != hipSuccess) return attr[full];
+    const char* nm = "k3s_eval+k1_stream_steps+k2_delta+k3p_pods";
+    return full ? klaunch(nm, step_one_launch<true>, dim3((unsigned)grid), dim3(kK3sThreads), kStepOneLds, st, k,
+                          (int32_t)nk, (int32_t)nk1, (int32_t)nk1pad, kr, a, ks, s.bnode, s.N, d, s.adj, pp)
+                : klaunch(nm, step_one_launch<false>, dim3((unsigned)grid), dim3(kK3sThreads), kStepOneLds, st, k,
+                          (int32_t)nk, (int32_t)nk1, (int32_t)nk1pad, kr, a, ks, s.bnode, s.N, d, s.adj, pp);
+}
+
+hipError_t launch_keys_reset(long long* keys, int64_t P, hipStream_t st) {
+    if (P <= 0 || !keys) return hipSuccess;
+    return klaunch("keys_reset", keys_reset, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, keys, P);
 }
 
 hipError_t launch_step_pairs(int shape, int64_t N, int64_t node_offset, int64_t P, long long* keys,

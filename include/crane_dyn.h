@@ -302,15 +302,20 @@ int crane_queue_create(int32_t device, int32_t ring_kind, crane_queue **out);
 /* Wait until every step enqueued on the queue has completed. */
 int crane_queue_wait(crane_queue *q);
 const char *crane_queue_last_error(const crane_queue *q);
+/* Dispatch packets (kernel launches) written to the queue since it was created. */
+uint64_t crane_queue_packets(const crane_queue *q);
 /* Waits for the queue, then frees it. */
 int crane_queue_destroy(crane_queue *q);
 /* crane_dyn_step_keys_async with the step's kernels on `q`: d_now / d_flags must be complete on
- * the device when called (written by finished work); d_keys is complete after crane_queue_wait.
+ * the device when called (written by finished work); d_keys is complete after crane_queue_wait
+ * (option step_defer 1 / 2: after one / two further steps of the engine on the queue, or
+ * crane_dyn_step_flush, and then crane_queue_wait).
  * The engine's own state changes wait for the queues it used: a queue must outlive the engine's
  * next state change, or be handed back first with crane_dyn_forget_queue. */
 int crane_dyn_step_keys_queue(crane_dyn *h, int64_t now_ns, int64_t hv_ts_ns, int64_t n_pods,
                               const int64_t *d_now_ns, const uint8_t *d_pod_flags, int64_t *d_keys, crane_queue *q);
-/* option step_defer: run the last step's deferred K3s now (on its queue; then wait for the queue) */
+/* option step_defer: run what the last steps left pending now, in order (on their queue: the older
+ * batch's K3s, the last batch's K1, its K3s; then wait for the queue) */
 int crane_dyn_step_flush(crane_dyn *h);
 /* Hand a queue back (waits for it): the engine no longer waits for it at its state changes. */
 int crane_dyn_forget_queue(crane_dyn *h, crane_queue *q);
@@ -347,10 +352,16 @@ const char *crane_dyn_version(void);
  *   "k2_sorted" 1 a time-ordered log (checked at upload): K2 reads the widest window's suffix only | 0 never
  *   "k2_delta" 1 ... and with k2_form 0, once anchored, only the bindings whose window rank changed since
  *     the anchor refresh (the anchor's dense counts + adjustments) | 0 every refresh re-counts the suffix
- *   "step_defer" 0 | 1: a step on a dispatch queue (crane_dyn_step_keys_queue) leaves its last kernel
- *     (K3s) to the engine's next step on that queue, which runs it inside its own first launch (one
- *     launch and one kernel boundary fewer per step); its keys are final once that launch, or
+ *   "step_defer" 0 | 1 | 2.  1: a step on a dispatch queue (crane_dyn_step_keys_queue) leaves its last
+ *     kernel (K3s) to the engine's next step on that queue, which runs it inside its own first launch
+ *     (one launch and one kernel boundary fewer per step); its keys are final once that launch, or
  *     crane_dyn_step_flush, or any other call on the engine, has run it and the queue completed it.
+ *     2: it leaves its node pass (K1) too: a step is then one launch holding this batch's K2 + K3p, the
+ *     previous batch's K1 and the K3s of the batch before (4 x 6 policies on the delta form, while the
+ *     launch is resident at once; else as 1), and a batch's keys are final two steps later, or after
+ *     crane_dyn_step_flush.  Key buffers: two in alternation never wait; the same buffer on
+ *     consecutive steps runs what is pending alone first.  Pending stages also run first when the
+ *     batch size or the node count changes, and before any other call on the engine
  *     The group sets it on its slots' engines and flushes at crane_dyn_group_sync
  *   "k1_stream" 1 the streamed step pass without dedupe-form K2 entries | 0 the record-holding fused pass
  *   "k1_tail" 0 its tail on one wave when the grid has >= 4096 blocks | 1 always | 4 on all four waves
@@ -384,9 +395,10 @@ int64_t crane_dyn_debug_trace(crane_dyn *h, int32_t which, int64_t max, uint64_t
  * per-batch collective (step_keys_async / schedule with the collective on) | 0 the steps' kernels
  * launched through HIP on the slots' streams | 1 on dispatch queues (crane_queue, one per slot and
  * device; the batch form crane_dyn_group_step_keys_batch orders its collective after them);
- * "dispatch_ring" 0 | 1 their ring_kind; "defer" 1 (default) | 0: engine option step_defer on the
- * queues' engines (a slot's K3s runs in its next step's first launch; crane_dyn_group_sync runs the
- * last ones — the caller alternates key buffers per slot, or the deferred K3s runs alone first);
+ * "dispatch_ring" 0 | 1 their ring_kind; "defer" 2 (default) | 1 | 0: engine option step_defer on the
+ * queues' engines (2: a slot's step is one launch, with its previous batch's K1 and the K3s of the
+ * batch before; 1: a slot's K3s runs in its next step's first launch; crane_dyn_group_sync runs the
+ * last ones — the caller alternates key buffers per slot, or the pending stages run alone first);
  * any other name goes to every engine.  Either way the batch's d_now / d_flags must be
  * complete on the devices when it is handed over (the group's streams and queues are its own). */
 typedef struct crane_dyn_group crane_dyn_group;
