@@ -286,7 +286,7 @@ struct crane_dyn {
         bool reset = false;  // its K3p left the keys' reset to this stage's launch
         int adj = 0;         // the adjustment buffer it reads and zeroes
     } pk1;
-    int64_t delta_chunks = 0;    // the delta form's workgroups of the last refresh
+    int64_t delta_chunks = 0;    // the last refresh's changed bindings in chunks of the one-launch step (kStepOneDeltaChunk)
     bool delta_first = false;    // the last refresh launched the delta form (with the step's K3p)
     bool defer_reset = false;    // this step's keys are what a pending K3s still merges into: if the
                                  // step goes out as one launch, K3p leaves their reset to the next
@@ -658,7 +658,7 @@ static int hot_delta_locked(crane_dyn* h, int64_t Bk, const HotCutoffs& pcut, hi
         }
         if (pods_done) *pods_done = pods != nullptr && pods->P > 0;
         h->delta_first = true;
-        h->delta_chunks = (L + 1023) / 1024;
+        h->delta_chunks = (L + kStepOneDeltaChunk - 1) / kStepOneDeltaChunk;
     }
     h->dl_adj_dirty[ab] = true;  // (until the node pass reads and zeroes the adjustments)
     h->dl_pending = true;

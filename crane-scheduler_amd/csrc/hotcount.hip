@@ -224,7 +224,8 @@ hipError_t launch_hot_count_delta(const int32_t* bnode, int64_t N, const HotDelt
     const int64_t grid = pp.ntiles + nb;
     if (grid == 0) return hipSuccess;
     if (grid >= (1LL << 31)) return hipErrorInvalidValue;
-    size_t lds = sizeof(uint32_t) * 2 * (size_t)kDeltaSlots + sizeof(uint16_t) * kDeltaMaxWin * kDeltaChunk;
+    size_t lds = delta_lds_bytes(kDeltaChunk, BT);  // (k2_delta_body<BT>'s layout)
+    static_assert(delta_lds_bytes(kDeltaChunk, BT) <= 64 * 1024, "within a workgroup's LDS");
     if (pp.ntiles > 0) lds = std::max(lds, kK3pLds);
     return klaunch(pp.ntiles > 0 ? "k2_delta+k3p_pods" : "k2_delta", k2_delta_pods<BT>, dim3((unsigned)grid), dim3(BT),
                    lds, st, bnode, N, d, adj, pp);

@@ -372,8 +372,10 @@ struct StepOne {
 };
 bool step_one_has(int shape);
 // workgroups of such a launch, and how many of them a compute unit holds at once (from the
-// kernel's LDS union and its 512-lane workgroups at <= 72 VGPRs): the engine takes the form only
-// when the whole launch is resident (every body's span is then one workgroup's chain)
+// kernel's LDS union and its 256-lane workgroups): the engine takes the form only when the whole
+// launch is resident (every body's span is then one workgroup's chain).  Its delta form takes
+// chunks of kStepOneDeltaChunk changed bindings.
+constexpr int kStepOneDeltaChunk = 512;
 int64_t step_one_workgroups(int64_t nk3s, int64_t N_k1, int64_t ntiles, int64_t delta_len);
 extern const int kStepOneWgPerCu;
 hipError_t launch_step_one(const StepOne& s, hipStream_t st);

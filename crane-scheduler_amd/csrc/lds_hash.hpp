@@ -69,7 +69,8 @@ __device__ __forceinline__ uint32_t wave_aggregate(const int32_t* key, int32_t* 
 }
 
 // ---------------------------------------------------------------- delta form
-// (kernels.hpp HotDelta.)  Per workgroup 1024 changed bindings.  A binding whose position is
+// (kernels.hpp HotDelta.)  Per workgroup CHUNK changed bindings (1024 in the form's own launches,
+// 512 in the one-launch queue step's 256-lane workgroups, step.hip).  A binding whose position is
 // inside window rank k at one of the two times and outside at the other changes that rank's
 // count by one: key (node * 8 + k) * 2 + sign (sign 1: it left, -1; 0: it entered, +1) — one key
 // per crossed cutoff, at most two with two windows (the form's limit, kDeltaMaxWin).  Keys are
@@ -78,31 +79,44 @@ __device__ __forceinline__ uint32_t wave_aggregate(const int32_t* key, int32_t* 
 // per bucket: K1 turns them into bucket adjustments (adj[b] - adj[b + 1]).  Counts are modulo
 // 2^32: anchor + adjustment is the exact count.
 constexpr int kDeltaChunk = 1024;
-constexpr int kDeltaSlots = 4 * kDeltaChunk;  // two per key, at most two keys per binding
+// hash slots of a chunk: two per key, at most two keys per binding
+constexpr int delta_slots(int chunk) { return 2 * kDeltaMaxWin * chunk; }
+// The body's dynamic LDS: the keys and the counts (a word per slot each), then uniq, a segment
+// of (key slots per thread) x 64 slot numbers per wave.  The launchers size the segment with it.
+constexpr size_t delta_lds_bytes(int chunk, int threads) {
+    return sizeof(uint32_t) * 2 * (size_t)delta_slots(chunk) +
+           sizeof(uint16_t) * (size_t)(threads / 64) * (size_t)(chunk / threads * kDeltaMaxWin * 64);
+}
 
-template <int BT>
+template <int BT, int CHUNK = kDeltaChunk>
 __device__ __forceinline__ void k2_delta_body(const int32_t blk, const int32_t* __restrict__ bnode, int64_t N,
                                               const HotDelta& d, uint32_t* __restrict__ adj) {
-    constexpr int kPer = kDeltaChunk / BT;
+    static_assert(CHUNK % BT == 0 && BT % 64 == 0, "whole bindings per lane, whole waves");
+    constexpr int kSlots = delta_slots(CHUNK);
+    static_assert((kSlots & (kSlots - 1)) == 0 && kSlots <= 65536, "hash_add masks the slot; uniq holds it in 16 bits");
+    constexpr int kPer = CHUNK / BT;
     constexpr int kKeys = kPer * kDeltaMaxWin;  // key slots per thread: (binding, rank)
+    static_assert(sizeof(uint32_t) * 2 * (size_t)kSlots + sizeof(uint16_t) * (BT / 64) * (kKeys * 64) ==
+                      delta_lds_bytes(CHUNK, BT),
+                  "the launchers' footprint is this layout's");
     extern __shared__ __attribute__((aligned(16))) uint32_t sh[];
     __shared__ uint32_t hist[32];  // (hash_add's bin counts: not read)
     int32_t* hkey = reinterpret_cast<int32_t*>(sh);
-    uint32_t* hcnt = sh + kDeltaSlots;
-    uint16_t* uniq = reinterpret_cast<uint16_t*>(hcnt + kDSlots);
+    uint32_t* hcnt = sh + kSlots;
+    uint16_t* uniq = reinterpret_cast<uint16_t*>(hcnt + kSlots);
     const int64_t L = d.start[d.n_rng];
     int64_t pos[kPer];
     int32_t nd[kPer];
 #pragma unroll
     for (int u = 0; u < kPer; ++u) {
-        const int64_t t = (int64_t)blk * kDeltaChunk + u * BT + threadIdx.x;
+        const int64_t t = (int64_t)blk * CHUNK + u * BT + threadIdx.x;
         int k = 0;
         for (int r = 1; r < d.n_rng; ++r) k += t >= d.start[r] ? 1 : 0;
         pos[u] = d.lo[k] + (t - d.start[k]);
         nd[u] = bnode[t < L ? pos[u] : d.lo[0]];  // (unconditional load, clamped)
         if (t >= L) nd[u] = -1;
     }
-    for (int i = threadIdx.x; i < kDeltaSlots; i += BT) {
+    for (int i = threadIdx.x; i < kSlots; i += BT) {
         hkey[i] = -1;
         hcnt[i] = 0;
     }
@@ -119,7 +133,7 @@ __device__ __forceinline__ void k2_delta_body(const int32_t blk, const int32_t* 
         }
     }
     uint16_t* useg = uniq + (threadIdx.x >> 6) * (kKeys * 64);
-    const uint32_t nw = wave_aggregate<kDeltaSlots, kKeys>(key, hkey, hcnt, hist, 24, useg);
+    const uint32_t nw = wave_aggregate<kSlots, kKeys>(key, hkey, hcnt, hist, 24, useg);
     __syncthreads();
     for (uint32_t i = threadIdx.x & 63; i < nw; i += 64) {  // this wave's new keys
         const int s = useg[i];

@@ -92,8 +92,8 @@ __global__ __launch_bounds__(kStepSeg) void k3a_steps(const NodeRec<PD, PR>* __r
 }
 
 // ---------------------------------------------------------------- K3s
-// Workgroup = 4 waves, one 1024-pod tile of K3p's sorted order (thread x holds
-// slots u * 256 + x); kind 0 pods are slots [0, cn), kind 1 [cn, cn + cd),
+// Workgroup = TH lanes, one 1024-pod tile of K3p's sorted order (thread x holds
+// slots u * TH + x); kind 0 pods are slots [0, cn), kind 1 [cn, cn + cd),
 // each sorted by now.  The R workgroups of a tile split the producer blocks:
 // m per workgroup, LPB lanes per block (the block's leader does the searches,
 // all its lanes share the record work).
@@ -114,10 +114,10 @@ __global__ __launch_bounds__(kStepSeg) void k3a_steps(const NodeRec<PD, PR>* __r
 // per workgroup.
 // 8 waves (512 lanes, 2 pods per lane) against 4: K3s 10.6 -> 9.6 us at config 3, 65.4 ->
 // 61 us at config 4 on one GPU, same box (profiles/r06/ab/k1_first_entry_rows_dropped_k3s_8waves.txt)
+// (K3s's own kernels; the one-launch queue step runs the body at kStepOneThreads)
 constexpr int kK3sWaves = 8;
 constexpr int kK3sThreads = kK3sWaves * 64;
-constexpr int kK3sPPL = 1024 / kK3sThreads;         // pods per lane
-constexpr int kK3sPods = kK3sThreads * kK3sPPL;     // pods per workgroup (= kPodTile)
+constexpr int kK3sPods = 1024;                      // pods per workgroup (= kPodTile)
 // producer blocks per workgroup aimed for (launches over kMaxWg workgroups are capped first):
 // 64 -> config 3 (391 blocks) and the config-4 shard (489) take 8 workgroups per tile.  Round 3,
 // same box (option k3s_blocks, tools/gpu_r03k3.sh / gpu_r03k3b.sh): shard 0.0343 -> 0.0300 ms
@@ -133,7 +133,6 @@ constexpr int kK3sListBlk = 64;
 constexpr int kSearchBucketBits = 8, kSearchBuckets = 1 << kSearchBucketBits;  // K3S_BUCKETS: per kind
 constexpr int kK3sRecList = 512;
 constexpr int kK3sPieceList = 512;
-static_assert(kK3sMaxBlk <= kK3sThreads, "at least one lane per producer block");
 static_assert(4 * kK3sListBlk <= 256, "list entries index the item map in 8 bits");
 static_assert(kK3sPods == kPodTile, "a workgroup resolves one K3p tile");
 
@@ -213,6 +212,10 @@ struct K3sLds {
 #endif
 };
 
+// TH lanes per workgroup, 1024 / TH pods per lane: 512 in K3s's own kernels, 256 in the one-launch
+// queue step (step_one_launch), whose workgroups then place seven to a compute unit.  Nothing a
+// lane count could change reaches the keys: every result is a maximum.
+template <int TH>
 __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, const int32_t* __restrict__ perm,
                                          const int64_t* __restrict__ pnow, const int64_t* __restrict__ tile_mm,
                                          int64_t P, int64_t node_offset, int32_t R, long long* __restrict__ keys,
@@ -224,6 +227,8 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
     int32_t* const wjl = lds.wjl;
     int32_t* const wpl = lds.wpl;
     uint8_t* const imap = lds.imap;
+    static_assert(kK3sPods % TH == 0 && TH % 64 == 0 && kK3sMaxBlk <= TH, "whole pods per lane, a lane per producer block");
+    constexpr int kPPL = kK3sPods / TH;  // pods per lane
 #if K3S_BUCKETS
     int32_t(*const sfirst)[kSearchBuckets + 1] = lds.sfirst;
 #endif
@@ -256,7 +261,7 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
         m = min(st.nblk, k0 + per) - k0;
     }
     int32_t lpb = 64;
-    while (lpb > 1 && lpb * m > kK3sThreads) lpb >>= 1;
+    while (lpb > 1 && lpb * m > TH) lpb >>= 1;
     const int32_t j = threadIdx.x / lpb, sub = threadIdx.x & (lpb - 1);
     const bool own = j < m;
     const int64_t ob = xc + (int64_t)stride * (k0 + j);
@@ -272,29 +277,26 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
         if (st.rows) row = st.rows[grp * st.nblk + ob];
         if (st.prow) prow = st.prow[grp * st.nblk + ob];
     }
-    bool live[kK3sPPL], ds[kK3sPPL];
-    int32_t pod[kK3sPPL];
     // every pod load issued before the first LDS store waits for one (unconditional, clamped
     // slot): a conditional load per pod made each store wait for its own round trip
-    int32_t praw[kK3sPPL];
-    int64_t pn[kK3sPPL];
+    // (kept per pod: its perm word — pod index, bit 31 = DaemonSet — 0 for a slot past the batch)
+    int32_t praw[kPPL];
+    int64_t pn[kPPL];
 #pragma unroll
-    for (int u = 0; u < kK3sPPL; ++u) {
-        const int64_t slot = grp * kK3sPods + u * kK3sThreads + threadIdx.x;
-        live[u] = slot < P;
-        const int64_t sc = live[u] ? slot : 0;
+    for (int u = 0; u < kPPL; ++u) {
+        const int64_t slot = grp * kK3sPods + u * TH + threadIdx.x;
+        const int64_t sc = slot < P ? slot : 0;
         praw[u] = perm[sc];
         pn[u] = pnow[sc];
     }
 #pragma unroll
-    for (int u = 0; u < kK3sPPL; ++u) {
-        tt[u * kK3sThreads + threadIdx.x] = live[u] ? pn[u] : INT64_MAX;
-        const int32_t pr = live[u] ? praw[u] : 0;
-        ds[u] = pr < 0;
-        pod[u] = pr & 0x7FFFFFFF;
+    for (int u = 0; u < kPPL; ++u) {
+        const bool live = grp * kK3sPods + u * TH + threadIdx.x < P;
+        tt[u * TH + threadIdx.x] = live ? pn[u] : INT64_MAX;
+        if (!live) praw[u] = 0;
     }
     const int64_t tsv = ts[lane < kTileStat ? lane : 0];
-    for (int i = threadIdx.x; i < 2 * kK3sPods; i += kK3sThreads) tree[i] = -1;
+    for (int i = threadIdx.x; i < 2 * kK3sPods; i += TH) tree[i] = -1;
     if (threadIdx.x < 2) umax[threadIdx.x] = -1;
     auto stat = [&](int k) {
         const uint32_t lo32 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tsv, k);
@@ -377,15 +379,19 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
     __syncthreads();  // tt, tree, umax initialised; the counts in
     CRANE_TSTAMP(st.trace, b, 1);
     const int32_t E = 4 * m;
-    // the bucket table (K3S_BUCKETS): lane (T, k) searches bucket k's first slot of kind T, all at
-    // once (one search's time, wave 0 after its prefix), ordered by the next barrier
+    // the bucket table (K3S_BUCKETS): a lane per (kind T, bucket k) searches bucket k's first slot
+    // of kind T (512 lanes: all at once, one search's time, wave 0 after its prefix; 256: two
+    // rounds), ordered by the next barrier
     auto bucket_table = [&]() {
 #if K3S_BUCKETS
-        static_assert(kK3sThreads == 2 * kSearchBuckets, "a lane per (kind, bucket)");
-        const int T = threadIdx.x / kSearchBuckets, k = threadIdx.x % kSearchBuckets;
-        if (klo[T] < khi[T]) {
-            sfirst[T][k] = slot_lower(tt, klo[T], khi[T], tlo[T] + ((int64_t)k << sbs[T]));
-            if (k == 0) sfirst[T][kSearchBuckets] = khi[T];
+        static_assert(2 * kSearchBuckets % TH == 0, "whole rounds over (kind, bucket)");
+#pragma unroll
+        for (int q = threadIdx.x; q < 2 * kSearchBuckets; q += TH) {
+            const int T = q / kSearchBuckets, k = q % kSearchBuckets;
+            if (klo[T] < khi[T]) {
+                sfirst[T][k] = slot_lower(tt, klo[T], khi[T], tlo[T] + ((int64_t)k << sbs[T]));
+                if (k == 0) sfirst[T][kSearchBuckets] = khi[T];
+            }
         }
 #endif
     };
@@ -419,50 +425,56 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
     const int32_t i0 = rec_list ? 0 : nrec, i1 = piece_list ? total : nrec;  // (workgroup-uniform)
     if (i1 > i0) {
         // the entries' items into the map (an entry's lane writes its run; E <= 256 entries)
-        for (int32_t e = threadIdx.x; e < E; e += kK3sThreads) {
+        for (int32_t e = threadIdx.x; e < E; e += TH) {
             const int32_t a = max(wpre[e], i0), z = min(wpre[e + 1], i1);
             for (int32_t i = a; i < z; ++i) imap[i - i0] = (uint8_t)e;
         }
         __syncthreads();
         // every item of this lane: its entry, then its record / piece loads all in flight, then the
-        // searches and the tree
-        constexpr int kU = (kK3sRecList + kK3sPieceList) / kK3sThreads;
-        Step1 r1[kU];
-        Mid pm[kU];
-        int32_t ee[kU];
+        // searches and the tree.  Two items of a lane at a time: four items' records in registers
+        // cost the 256-lane form a wave per SIMD; a pass past the last item is skipped
+        // (workgroup-uniform; at config 3 the median slice has 64 items, the largest 125)
+        constexpr int kU = 2, kPass = (kK3sRecList + kK3sPieceList) / (kU * TH);
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int32_t it = i0 + u * kK3sThreads + (int32_t)threadIdx.x;
-            ee[u] = -1;
-            if (it >= i1) continue;
-            const int32_t e = imap[it - i0];
-            ee[u] = e;
-            const bool rec = e < 2 * m;
-            const int32_t ej = rec ? e : e - 2 * m, jb = ej >> 1, T = ej & 1, idx = it - wpre[e];
-            const int64_t obj = xc + (int64_t)stride * (k0 + jb);
-            if (rec) r1[u] = (st.single + s1_at(st, T, obj))[wjl[2 * jb + T] + idx];
-            else pm[u] = st.mid[(int64_t)T * st.mpad + obj * st.mstride + wpl[ej] + idx];
-        }
+        for (int h = 0; h < kPass; ++h) {
+            if (i0 + h * kU * TH >= i1) break;
+            Step1 r1[kU];
+            Mid pm[kU];
+            int32_t ee[kU];
 #pragma unroll
-        for (int u = 0; u < kU; ++u) {
-            const int32_t e = ee[u];
-            if (e < 0) continue;
-            const bool rec = e < 2 * m;
-            const int T = (rec ? e : e - 2 * m) & 1;
-            if (rec) {
-                // a one-step record stepping inside (lo, hi]: split the kind's slots
-                const int32_t sp = find(T, r1[u].bp);
-                if (r1[u].k0 >= 0) tree_max(tree, klo[T], sp, r1[u].k0);
-                if (r1[u].k1 >= 0) tree_max(tree, sp, khi[T], r1[u].k1);
-                upd = true;
-            } else {
-                // a middle piece: covering -> uniform, overlapping partly -> range maximum over
-                // the slots with s <= now < e
-                const Mid& q = pm[u];
-                if (q.s <= tlo[T] && q.e > thi[T]) um[T] = max(um[T], q.key);
-                else if (q.s <= thi[T] && q.e > tlo[T]) {
-                    tree_max(tree, find(T, q.s), find(T, q.e), q.key);
+            for (int u = 0; u < kU; ++u) {
+                const int32_t it = i0 + (h * kU + u) * TH + (int32_t)threadIdx.x;
+                ee[u] = -1;
+                if (it >= i1) continue;
+                const int32_t e = imap[it - i0];
+                ee[u] = e;
+                const bool rec = e < 2 * m;
+                const int32_t ej = rec ? e : e - 2 * m, jb = ej >> 1, T = ej & 1, idx = it - wpre[e];
+                const int64_t obj = xc + (int64_t)stride * (k0 + jb);
+                if (rec) r1[u] = (st.single + s1_at(st, T, obj))[wjl[2 * jb + T] + idx];
+                else pm[u] = st.mid[(int64_t)T * st.mpad + obj * st.mstride + wpl[ej] + idx];
+            }
+#pragma unroll
+            for (int u = 0; u < kU; ++u) {
+                const int32_t e = ee[u];
+                if (e < 0) continue;
+                const bool rec = e < 2 * m;
+                const int T = (rec ? e : e - 2 * m) & 1;
+                if (rec) {
+                    // a one-step record stepping inside (lo, hi]: split the kind's slots
+                    const int32_t sp = find(T, r1[u].bp);
+                    if (r1[u].k0 >= 0) tree_max(tree, klo[T], sp, r1[u].k0);
+                    if (r1[u].k1 >= 0) tree_max(tree, sp, khi[T], r1[u].k1);
                     upd = true;
+                } else {
+                    // a middle piece: covering -> uniform, overlapping partly -> range maximum over
+                    // the slots with s <= now < e
+                    const Mid& q = pm[u];
+                    if (q.s <= tlo[T] && q.e > thi[T]) um[T] = max(um[T], q.key);
+                    else if (q.s <= thi[T] && q.e > tlo[T]) {
+                        tree_max(tree, find(T, q.s), find(T, q.e), q.key);
+                        upd = true;
+                    }
                 }
             }
         }
@@ -515,29 +527,39 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
     const bool tree_used = __syncthreads_or(upd);
     CRANE_TSTAMP(st.trace, b, 3);
     // a pod's key: the max over its leaf's ancestors (every level's load issued at once, for
-    // all of the lane's pods: one LDS round trip, not a dependent walk per pod)
+    // two of the lane's pods: one LDS round trip, not a dependent walk per pod; the 256-lane
+    // form's four pods in two such passes, so that 22 ancestor words are live, not 44)
     constexpr int kLevels = 11;  // leaves at kK3sPods + slot, root at 1
     static_assert(kK3sPods == 1 << (kLevels - 1), "a segment tree over the tile's 1024 slots");
-    int32_t anc[kK3sPPL][kLevels];
-    if (tree_used) {
+    constexpr int kV = 2;
+    static_assert(kPPL % kV == 0, "whole passes");
 #pragma unroll
-        for (int u = 0; u < kK3sPPL; ++u)
-#pragma unroll
-            for (int l = 0; l < kLevels; ++l) anc[u][l] = tree[(u * kK3sThreads + threadIdx.x + kK3sPods) >> l];
-    }
-#pragma unroll
-    for (int u = 0; u < kK3sPPL; ++u) {
-        int32_t best = umax[ds[u] ? 1 : 0];
+    for (int h = 0; h < kPPL / kV; ++h) {
+        int32_t anc[kV][kLevels];
         if (tree_used) {
 #pragma unroll
-            for (int l = 0; l < kLevels; ++l) best = max(best, anc[u][l]);
+            for (int v = 0; v < kV; ++v)
+#pragma unroll
+                for (int l = 0; l < kLevels; ++l)
+                    anc[v][l] = tree[((h * kV + v) * TH + threadIdx.x + kK3sPods) >> l];
         }
-        if (live[u] && best >= 0) {
-            const int64_t sc = best >> 24;
-            const int64_t n = 0xFFFFFF - (best & 0xFFFFFF);
-            atomicMax(&keys[pod[u]],
-                      (long long)((sc << 32) | (int64_t)(0xFFFFFFFFull - (uint64_t)(node_offset + n))));
+#pragma unroll
+        for (int v = 0; v < kV; ++v) {
+            const int u = h * kV + v;
+            int32_t best = umax[praw[u] < 0 ? 1 : 0];
+            if (tree_used) {
+#pragma unroll
+                for (int l = 0; l < kLevels; ++l) best = max(best, anc[v][l]);
+            }
+            const bool live = grp * kK3sPods + u * TH + threadIdx.x < P;
+            if (live && best >= 0) {
+                const int64_t sc = best >> 24;
+                const int64_t n = 0xFFFFFF - (best & 0xFFFFFF);
+                atomicMax(&keys[praw[u] & 0x7FFFFFFF],
+                          (long long)((sc << 32) | (int64_t)(0xFFFFFFFFull - (uint64_t)(node_offset + n))));
+            }
         }
+        if (h + 1 < kPPL / kV) asm volatile("" ::: "memory");  // (the next pass's loads stay behind this one's)
     }
     CRANE_TSTAMP(st.trace, b, 4);
 }
@@ -560,7 +582,7 @@ __global__ __launch_bounds__(kK3sThreads) void k3s_eval(StepTables st, const int
     kernarg_warm<(int)sizeof(StepTables) + 64>();
 #endif
     __shared__ K3sLds lds;
-    k3s_body((int64_t)blockIdx.x, st, perm, pnow, tile_mm, P, node_offset, R, keys, lds);
+    k3s_body<kK3sThreads>((int64_t)blockIdx.x, st, perm, pnow, tile_mm, P, node_offset, R, keys, lds);
 }
 
 // The previous step's K3s and this step's first launch (the delta form's K2 + K3p's pod tiles)
@@ -590,7 +612,7 @@ __global__ __launch_bounds__(kK3sThreads) void k3s_delta_pods(K3sArgs k, int32_t
     const int64_t b = blockIdx.x;
     if (b < nk3s) {
         __shared__ K3sLds lds;
-        k3s_body(b, k.st, k.perm, k.pnow, k.tile_mm, k.P, k.node_offset, k.R, k.keys, lds);
+        k3s_body<kK3sThreads>(b, k.st, k.perm, k.pnow, k.tile_mm, k.P, k.node_offset, k.R, k.keys, lds);
         return;
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
@@ -602,61 +624,76 @@ __global__ __launch_bounds__(kK3sThreads) void k3s_delta_pods(K3sArgs k, int32_t
 // (kernels.hpp StepOne.)  Workgroups by blockIdx: K3s's first (nk3s = ngroups * R is a multiple
 // of 8 whenever nblk >= 8, so its XCD placement is its own launch's), then K1's blocks padded to
 // a multiple of 8 (K1 is fed its local index and count: block -> XCD as in its own launch, which
-// K3s's XCD groups rely on), then the pod tiles, then the delta form's chunks.  Workgroups are
-// 512 lanes; K1's body is 256: waves 4-7 of a K1 workgroup reset their slice of the keys and
-// return before the body's first barrier (a barrier waits only for the waves still running).
-// The bodies' LDS is one union carved from the dynamic segment.
+// K3s's XCD groups rely on), then the key reset's, the pod tiles, the delta form's chunks.
+// Workgroups are 256 lanes, K1's own size, and the bodies' LDS is one union carved from the
+// dynamic segment, no larger than K3s's: seven workgroups share a compute unit (28 waves at 7
+// per SIMD, 7 x (union + the bodies' static words) within 160 KiB), where 512-lane workgroups
+// holding a 1024-binding delta hash placed three — with four slots' launches in flight the
+// launches queued for those places.  K3s resolves four pods per lane, K3p sorts four, the delta
+// form takes chunks of kStepOneDeltaChunk bindings (two per lane, as its own launch).
+// The keys of K1's batch are reset by workgroups of their own (1024 keys each): off K1's chain.
 struct KeyReset {
     long long* keys;
     int64_t P;
 };
-constexpr size_t kDeltaLds = sizeof(uint32_t) * 2 * (size_t)kDeltaSlots + sizeof(uint16_t) * kDeltaMaxWin * kDeltaChunk;
+constexpr int kStepOneThreads = 256;
+constexpr int kResetPerWg = 4 * kStepOneThreads;  // keys per reset workgroup
+static_assert(kResetPerWg == kPodTile, "step_one_workgroups counts a reset workgroup per pod tile");
+constexpr size_t kStepOneDeltaLds = delta_lds_bytes(kStepOneDeltaChunk, kStepOneThreads);
 constexpr size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
-constexpr size_t kStepOneLds = cmax(cmax(sizeof(K1Lds<4, 6>), sizeof(K3sLds)), cmax(kK3pLds, kDeltaLds));
+constexpr size_t kStepOneLds = cmax(cmax(sizeof(K1Lds<4, 6>), sizeof(K3sLds)), cmax(kK3pLds, kStepOneDeltaLds));
 static_assert(kStepOneLds >= sizeof(K1Lds<4, 6>) && kStepOneLds >= sizeof(K3sLds) && kStepOneLds >= kK3pLds &&
-                  kStepOneLds >= kDeltaLds,
+                  kStepOneLds >= kStepOneDeltaLds,
               "the union holds the largest body");
-static_assert(kStepOneLds + 512 <= 53 * 1024, "three workgroups per compute unit (160 KiB)");
-// resident workgroups per compute unit: LDS (+ the bodies' few static words), and 8-wave
-// workgroups at 7 waves per SIMD
-const int kStepOneWgPerCu = (int)std::min<size_t>(160 * 1024 / (kStepOneLds + 512), 4 * (K1S_WAVES - 1) / kK3sWaves);
-// kernarg offsets (each argument at its natural alignment): K3sArgs, three counts, KeyReset, K1's
+static_assert(kStepOneLds == sizeof(K3sLds), "no body asks for more than K3s");
+// (+ 512: the bodies' static words — K3p's group counts, the delta form's bins)
+static_assert(7 * (kStepOneLds + 512) <= 160 * 1024, "seven workgroups per compute unit (160 KiB)");
+// resident workgroups per compute unit: LDS, and 4-wave workgroups at the waves per SIMD of the
+// instance built for fewer (any 4 x 6 policy: K1S_WAVES - 1; the shipped policy's places seven)
+const int kStepOneWgPerCu =
+    (int)std::min<size_t>(160 * 1024 / (kStepOneLds + 512), 4 * (K1S_WAVES - 1) / (kStepOneThreads / 64));
+// kernarg offsets (each argument at its natural alignment): K3sArgs, four counts, KeyReset, K1's
 constexpr int kOneK3sEnd = (int)sizeof(K3sArgs) + 16;
 constexpr int kOneK1End = kOneK3sEnd + (int)sizeof(KeyReset) + (int)sizeof(K1Args) + (int)sizeof(K1Step) + 8;
 constexpr int kOneEnd = kOneK1End + 16 + (int)sizeof(HotDelta) + 8 + (int)sizeof(PodPrep);
 
 template <bool FULL>
-// (the instance for any 4 x 6 policy needs 73 registers: built for 6 waves per SIMD, which holds
-// the same three 8-wave workgroups per compute unit)
-__global__ __launch_bounds__(kK3sThreads) __attribute__((amdgpu_waves_per_eu(FULL ? K1S_WAVES : K1S_WAVES - 1)))
-void step_one_launch(K3sArgs k, int32_t nk3s, int32_t nk1, int32_t nk1pad, KeyReset kr, K1Args a, K1Step step,
-                     const int32_t* __restrict__ bnode, int64_t N, HotDelta d, uint32_t* __restrict__ adj, PodPrep pp) {
+// (the instance for any 4 x 6 policy needs 73 registers: built for 6 waves per SIMD)
+__global__ __launch_bounds__(kStepOneThreads) __attribute__((amdgpu_waves_per_eu(FULL ? K1S_WAVES : K1S_WAVES - 1)))
+void step_one_launch(K3sArgs k, int32_t nk3s, int32_t nk1, int32_t nk1pad, int32_t nreset, KeyReset kr, K1Args a,
+                     K1Step step, const int32_t* __restrict__ bnode, int64_t N, HotDelta d, uint32_t* __restrict__ adj,
+                     PodPrep pp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_lds[];
     int64_t b = blockIdx.x;
     if (b < nk3s) {
 #if K3_KWARM
         kernarg_warm<kOneK3sEnd>();
 #endif
-        k3s_body(b, k.st, k.perm, k.pnow, k.tile_mm, k.P, k.node_offset, k.R, k.keys,
-                 *reinterpret_cast<K3sLds*>(dyn_lds));
+        k3s_body<kStepOneThreads>(b, k.st, k.perm, k.pnow, k.tile_mm, k.P, k.node_offset, k.R, k.keys,
+                                  *reinterpret_cast<K3sLds*>(dyn_lds));
         return;
     }
     b -= nk3s;
     if (b < nk1pad) {
         if (b >= nk1) return;
-        if (threadIdx.x >= 256) {
-            for (int64_t p = b * 256 + (threadIdx.x - 256); p < kr.P; p += (int64_t)nk1 * 256) kr.keys[p] = -1;
-            return;
-        }
         k1_stream_body<4, 6, FULL, kOneK1End>(a, step, b, nk1, *reinterpret_cast<K1Lds<4, 6>*>(dyn_lds));
         return;
     }
     b -= nk1pad;
+    if (b < nreset) {
+#pragma unroll
+        for (int u = 0; u < kResetPerWg / kStepOneThreads; ++u) {
+            const int64_t p = b * kResetPerWg + u * kStepOneThreads + threadIdx.x;
+            if (p < kr.P) kr.keys[p] = -1;
+        }
+        return;
+    }
+    b -= nreset;
 #if K3_KWARM
     kernarg_warm<kOneEnd, kOneK1End>();
 #endif
-    if (b < pp.ntiles) k3p_tile<kK3sThreads>(b, pp, dyn_lds);
-    else k2_delta_body<kK3sThreads>((int32_t)(b - pp.ntiles), bnode, N, d, adj);
+    if (b < pp.ntiles) k3p_tile<kStepOneThreads>(b, pp, dyn_lds);
+    else k2_delta_body<kStepOneThreads, kStepOneDeltaChunk>((int32_t)(b - pp.ntiles), bnode, N, d, adj);
 }
 
 __global__ __launch_bounds__(256) void keys_reset(long long* __restrict__ keys, int64_t P) {
@@ -728,8 +765,8 @@ hipError_t launch_k3s_delta_pods(int64_t N_k3s, int64_t node_offset, int64_t P_k
     if (grid >= (1LL << 31) || nk >= (1LL << 31)) return hipErrorInvalidValue;
     PodPrep pp{};
     if (pods.P > 0) pp = pods;
-    const size_t lds = std::max(kK3pLds, sizeof(uint32_t) * 2 * (size_t)kDeltaSlots +
-                                             sizeof(uint16_t) * kDeltaMaxWin * kDeltaChunk);
+    constexpr size_t lds = cmax(kK3pLds, delta_lds_bytes(kDeltaChunk, kK3sThreads));  // (k2_delta_body<kK3sThreads>'s)
+    static_assert(lds + sizeof(K3sLds) <= 64 * 1024, "beside K3s's static LDS in a workgroup's 64 KiB");
     static const hipError_t attr = hipFuncSetAttribute((const void*)k3s_delta_pods,
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (attr != hipSuccess) return attr;
@@ -740,9 +777,11 @@ hipError_t launch_k3s_delta_pods(int64_t N_k3s, int64_t node_offset, int64_t P_k
 
 bool step_one_has(int shape) { return shape == kShape4x6; }
 
+// (a steady state's K1 resets the keys of a batch as large as the one whose pods are sorted: a
+// reset workgroup per pod tile)
 int64_t step_one_workgroups(int64_t nk3s, int64_t N_k1, int64_t ntiles, int64_t delta_len) {
     const int64_t nk1 = (N_k1 + 255) / 256;
-    return nk3s + (nk1 + 7) / 8 * 8 + ntiles + (delta_len + kDeltaChunk - 1) / kDeltaChunk;
+    return nk3s + (nk1 + 7) / 8 * 8 + 2 * ntiles + (delta_len + kStepOneDeltaChunk - 1) / kStepOneDeltaChunk;
 }
 
 hipError_t launch_step_one(const StepOne& s, hipStream_t st) {
@@ -755,11 +794,13 @@ hipError_t launch_step_one(const StepOne& s, hipStream_t st) {
     const int64_t nk = k3s ? s.g.ngroups * s.g.R : 0;
     const int64_t nk1 = k1 ? (s.k1->N + 255) / 256 : 0, nk1pad = (nk1 + 7) / 8 * 8;
     const int64_t L = delta && s.d->n_rng > 0 ? s.d->start[s.d->n_rng] : 0;
-    const int64_t grid = nk + nk1pad + (pods ? s.pods->ntiles : 0) + (L + kDeltaChunk - 1) / kDeltaChunk;
+    const KeyReset kr{s.reset_keys, k1 && s.reset_keys && s.reset_P > 0 ? s.reset_P : 0};
+    const int64_t nreset = (kr.P + kResetPerWg - 1) / kResetPerWg;
+    const int64_t grid = nk + nk1pad + nreset + (pods ? s.pods->ntiles : 0) +
+                         (L + kStepOneDeltaChunk - 1) / kStepOneDeltaChunk;
     if (grid >= (1LL << 31)) return hipErrorInvalidValue;
     if (grid == 0) return hipSuccess;
     const K3sArgs k{s.st, s.perm, s.pnow, s.tile_mm, k3s ? s.P_k3s : 0, s.node_offset, s.g.R, s.keys_k3s};
-    const KeyReset kr{s.reset_keys, k1 && s.reset_keys ? s.reset_P : 0};
     const K1Args a = k1 ? *s.k1 : K1Args{};
     const K1Step ks = k1 ? *s.ks : K1Step{};
     const HotDelta d = delta ? *s.d : HotDelta{};
@@ -772,10 +813,10 @@ hipError_t launch_step_one(const StepOne& s, hipStream_t st) {
                             (int)kStepOneLds)};
     if (attr[full] != hipSuccess) return attr[full];
     const char* nm = "k3s_eval+k1_stream_steps+k2_delta+k3p_pods";
-    return full ? klaunch(nm, step_one_launch<true>, dim3((unsigned)grid), dim3(kK3sThreads), kStepOneLds, st, k,
-                          (int32_t)nk, (int32_t)nk1, (int32_t)nk1pad, kr, a, ks, s.bnode, s.N, d, s.adj, pp)
-                : klaunch(nm, step_one_launch<false>, dim3((unsigned)grid), dim3(kK3sThreads), kStepOneLds, st, k,
-                          (int32_t)nk, (int32_t)nk1, (int32_t)nk1pad, kr, a, ks, s.bnode, s.N, d, s.adj, pp);
+    return full ? klaunch(nm, step_one_launch<true>, dim3((unsigned)grid), dim3(kStepOneThreads), kStepOneLds, st, k,
+                          (int32_t)nk, (int32_t)nk1, (int32_t)nk1pad, (int32_t)nreset, kr, a, ks, s.bnode, s.N, d, s.adj, pp)
+                : klaunch(nm, step_one_launch<false>, dim3((unsigned)grid), dim3(kStepOneThreads), kStepOneLds, st, k,
+                          (int32_t)nk, (int32_t)nk1, (int32_t)nk1pad, (int32_t)nreset, kr, a, ks, s.bnode, s.N, d, s.adj, pp);
 }
 
 hipError_t launch_keys_reset(long long* keys, int64_t P, hipStream_t st) {
