@@ -211,7 +211,7 @@ struct crane_dyn {
     bool counts_pending = false;  // buckets hold K2 counts no node pass has consumed yet
     bool hx_pending = false;      // ... in the dedupe form: per-block entries in k2_sorted (hx_g)
     HotPart hx_g{};
-    // delta form (hot_delta_locked): dense anchor counts at suffix starts dl_pos (valid for log
+    // delta form (refresh_plan): dense anchor counts at suffix starts dl_pos (valid for log
     // version dl_log_ver, N dl_N), the adjustments of the next node pass (zero unless dl_adj_dirty)
     bool dl_valid = false, dl_pending = false;
     // two adjustment buffers: a K1 left pending (step_defer 2) still reads one while the next
@@ -260,37 +260,40 @@ struct crane_dyn {
     DevBuf<int32_t> sperm[3];
     DevBuf<int64_t> stile[3], spnow[3], sbatch;
     int sbatch_par = 0;
-    // option step_defer: the last step's K3s, not launched yet (its queue, tables, pod set, keys)
-    struct PendK3s {
-        bool on = false;
+    // option step_defer: the stages the last steps on a dispatch queue planned and did not launch,
+    // all on one queue (a step on another drains them first).  k3s: a batch's K3s (option 1, or the
+    // older batch of option 2).  k1: the next batch's K1 (option 2) with its arguments by value —
+    // the policy's window cutoffs, the hot values' stamp, the adjustment buffer: the next step's
+    // refresh rewrites the engine's own — and the K3s that follows it
+    struct StepPipe {
+        struct K3s {
+            bool on = false;
+            K3sBatch b{};
+            int tset = 0;  // the table set b.st points into
+        } k3s;
+        struct K1 {
+            bool on = false;
+            K1Args a{};
+            K1Step ks{};
+            K3s next;
+            bool reset = false;  // its K3p left the keys' reset to this stage's launch
+            int adj = 0;         // the adjustment buffer it reads and zeroes
+        } k1;
         crane_queue* q = nullptr;
-        StepTables stt{};
-        StepGeometry g{};
-        const int32_t* perm = nullptr;
-        const int64_t* pnow = nullptr;
-        const int64_t* tiles = nullptr;
-        int64_t P = 0;
-        long long* keys = nullptr;
-        int tset = 0;  // the table set stt points into
-        int64_t N = 0;  // the node count it was planned for
-    } pend;
-    // step_defer 2: the last step's K1, not launched yet, with its arguments by value (the policy's
-    // window cutoffs, the hot values' stamp, the adjustment buffer: the next step's refresh rewrites
-    // the engine's own), and the K3s that follows it.  pend, when on too, is the batch before
-    struct PendK1 {
-        bool on = false;
-        crane_queue* q = nullptr;
-        K1Args a{};
-        K1Step ks{};
-        PendK3s next;
-        bool reset = false;  // its K3p left the keys' reset to this stage's launch
-        int adj = 0;         // the adjustment buffer it reads and zeroes
-    } pk1;
-    int64_t delta_chunks = 0;    // the last refresh's changed bindings in chunks of the one-launch step (kStepOneDeltaChunk)
-    bool delta_first = false;    // the last refresh launched the delta form (with the step's K3p)
-    bool defer_reset = false;    // this step's keys are what a pending K3s still merges into: if the
-                                 // step goes out as one launch, K3p leaves their reset to the next
-    bool reset_deferred = false; // ... and it did
+        bool any() const { return k3s.on || k1.on; }
+        crane_queue* queue() const { return q; }  // (while any())
+        // the youngest batch pending (its P, N and keys are what the next step's plan is held against)
+        const K3sBatch& last() const { return k1.on ? k1.next.b : k3s.b; }
+        // the table set no pending K3s reads: the next step's K1 writes it
+        int free_tset() const { return k1.on ? k1.next.tset ^ 1 : k3s.on ? k3s.tset ^ 1 : 0; }
+        // the adjustment buffer a pending K1 still reads (the next refresh takes the other), or -1
+        int held_adj() const { return k1.on ? k1.adj : -1; }
+        // the K1 stage was launched: its batch's K3s is now the older one
+        void advance() {
+            k3s = k1.next;
+            k1.on = false;
+        }
+    } pipe;
     DevBuf<int64_t> sel_fth, sel_win, sel_state;  // framework selection (select.hip)
     DevBuf<long long> sel_keys;
     DevBuf<unsigned char> stp_dev;  // node answer tables (crane_dyn_node_steps): bp, ns, ff, score
@@ -424,7 +427,7 @@ struct Locked {
     explicit Locked(crane_dyn* h, bool keep_pending = false) : g(h->mu), prev(tl_ktimer) {
         tl_ktimer = h->prof ? &h->timer : nullptr;
         const bool stale = h->sd && (h->sd_node_ver != h->sd->node_ver || h->sd_log_ver != h->sd->log_ver);
-        if ((!keep_pending || stale) && (h->pend.on || h->pk1.on)) rc = flush_pending(h);
+        if ((!keep_pending || stale) && h->pipe.any()) rc = flush_pending(h);
         if (!rc && h->sd && (h->sd_node_ver != h->sd->node_ver || h->sd_log_ver != h->sd->log_ver)) rc = adopt(h);
     }
     ~Locked() { tl_ktimer = prev; }
@@ -523,171 +526,50 @@ static int zero_for(crane_dyn* h, uint32_t* p, size_t n, hipStream_t st) {
     return CRANE_OK;
 }
 
-// Delta form of a time-ordered log's refresh (kernels.hpp HotDelta), after the suffix search
-// (h->pos_s): counts = the anchor's dense counts + the changed bindings' adjustments.  The first
-// refresh after the log or the node count changed, or one whose changed bindings pass half the
-// widest window's suffix, re-anchors here: the large form writes its dense counts as the new
-// anchor (adjustments zero).  *done false: the form does not apply (the caller's forms run).
-static int hot_delta_locked(crane_dyn* h, int64_t Bk, const HotCutoffs& pcut, hipStream_t st, const PodPrep* pods,
-                            bool* pods_done, bool* done) {
-    const DevPolicy& dp = h->dp;
-    const int nw = dp.n_win;
-    *done = false;
-    if (h->N <= 0 || h->N >= (1LL << 27) || nw < 1 || nw > kDeltaMaxWin) return CRANE_OK;
-    const size_t nb = (size_t)nw * (size_t)h->N;
-    const bool anchored = h->dl_valid && h->dl_log_ver == h->sd_log_ver && h->dl_N == h->N && h->dl_B == h->B;
-    // the changed positions: per window rank r, between the anchor's and this refresh's suffix
-    // starts; merged
-    HotDelta d{};
-    d.n_win = nw;
-    int64_t L = 0;
-    if (anchored) {
-        std::pair<int64_t, int64_t> rg[kMaxWin];
-        int n = 0;
-        for (int r = 0; r < nw; ++r) {
-            d.a[r] = h->dl_pos[r];
-            d.p[r] = h->pos_s[r];
-            const int64_t lo = std::min(d.a[r], d.p[r]), hi = std::max(d.a[r], d.p[r]);
-            if (hi > lo) rg[n++] = {lo, hi};
-        }
-        std::sort(rg, rg + n);
-        int m = 0;
-        for (int i = 0; i < n; ++i) {
-            if (m > 0 && rg[i].first <= rg[m - 1].second) rg[m - 1].second = std::max(rg[m - 1].second, rg[i].second);
-            else rg[m++] = rg[i];
-        }
-        d.n_rng = m;
-        d.start[0] = 0;
-        for (int k = 0; k < m; ++k) {
-            d.lo[k] = rg[k].first;
-            d.start[k + 1] = d.start[k] + (rg[k].second - rg[k].first);
-        }
-        L = d.start[m];
-    }
-    // (a pending K1 holds one adjustment buffer until its launch: this refresh takes the other)
-    const int ab = h->pk1.on ? h->pk1.adj ^ 1 : h->dl_cur;
-    h->dl_cur = ab;
-    DevBuf<uint32_t>& adj = h->dl_adj[ab];
-    // (step_defer 2: the other buffer too, up front, unless a pending K1 holds it — an allocation
-    // and a fill wait for the queue, and belong to an engine's first step, not its third)
-    for (int b : {ab, ab ^ 1}) {
-        if (b != ab && (h->opt.step_defer != 2 || !tl_aql || h->pk1.on)) break;
-        DevBuf<uint32_t>& x = h->dl_adj[b];
-        if (x.n < nb) {
-            HIPTRY(h, x.reserve(nb));
-            h->dl_adj_dirty[b] = true;
-        }
-        if (h->dl_adj_dirty[b]) {  // (an earlier refresh's adjustments no node pass consumed, or a new buffer)
-            if (int rc = zero_for(h, x.p, x.n, st)) return rc;
-            h->dl_adj_dirty[b] = false;
-        }
-    }
-    h->dl_zero = false;
-    // every form but the delta launch below: what is pending runs first (the re-anchor rewrites the
-    // anchor a pending K1 reads; that K1 belongs in front of this step's launches in any case)
-    if (h->pk1.on && (Bk == 0 || !anchored || 2 * L > Bk))
-        if (int rc = flush_pending(h)) return rc;
-    if (Bk == 0) {
-        // no binding inside any window: every count is zero — K1 reads the (clean) adjustments as
-        // the anchor too; the anchor itself is kept for the next refresh
-        h->dl_zero = true;
-    } else if (!anchored || 2 * L > Bk) {
-        const HotPart gl = hot_large_geometry(Bk, h->N, nw);
-        const HotPart gf = hot_large_geometry(h->B, h->N, nw);
-        if (!gl.ok) return CRANE_OK;
-        HIPTRY(h, h->dl_base.reserve(nb));
-        h->dl_valid = false;
-        HIPTRY(h, h->k2_sorted.reserve(std::max(hot_dedupe_scratch(gl), gf.ok ? hot_dedupe_scratch(gf) : 0)));
-        HIPTRY(h, launch_hot_count_large(h->sd->bnode.p + h->pos_s[0], h->sd->bts.p, Bk, h->N, pcut, gl,
-                                         h->k2_sorted.p, h->dl_base.p, h->n_cu, st, kK2lThreads));
-        std::memcpy(h->dl_pos, h->pos_s, sizeof(int64_t) * nw);
-        h->dl_valid = true;
-        h->dl_log_ver = h->sd_log_ver;
-        h->dl_N = h->N;
-        h->dl_B = h->B;
-    } else {
-        crane_dyn::PendK3s& pk = h->pend;
-        crane_dyn::PendK1& k1 = h->pk1;
-        const bool mine = tl_aql && pods && pods->P > 0;
-        if (k1.on && !(mine && k1.q == tl_aql &&
-                       step_one_workgroups(pk.on ? pk.g.ngroups * pk.g.R : 0, h->N, pods->ntiles, L) <=
-                           (int64_t)kStepOneWgPerCu * h->n_cu)) {
-            // (a launch that is not resident at once — a time jump's many changed bindings —
-            // keeps the launches apart)
-            if (int rc = flush_pending(h)) return rc;
-        }
-        if (k1.on) {
-            // the whole step as one launch (option step_defer 2: step.hip step_one_launch): K3s of the
-            // batch two steps back, the previous batch's K1, this batch's delta form + K3p
-            StepOne s{};
-            s.N = h->N;
-            s.node_offset = h->node_offset;
-            if (pk.on) {
-                s.P_k3s = pk.P;
-                s.keys_k3s = pk.keys;
-                s.st = pk.stt;
-                s.g = pk.g;
-                s.perm = pk.perm;
-                s.pnow = pk.pnow;
-                s.tile_mm = pk.tiles;
-            }
-            s.k1 = &k1.a;
-            s.ks = &k1.ks;
-            s.reset_keys = k1.reset ? k1.next.keys : nullptr;
-            s.reset_P = k1.next.P;
-            s.bnode = h->sd->bnode.p;
-            s.d = &d;
-            s.adj = adj.p;
-            PodPrep pp = *pods;
-            if (h->defer_reset) pp.keys = nullptr;
-            s.pods = &pp;
-            HIPTRY(h, launch_step_one(s, st));
-            h->reset_deferred = h->defer_reset;
-            pk = k1.next;
-            k1.on = false;
-        } else if (pk.on && mine && pk.q == tl_aql) {
-            // the previous step's K3s in this launch (option step_defer: step.hip k3s_delta_pods)
-            HIPTRY(h, launch_k3s_delta_pods(h->N, h->node_offset, pk.P, pk.keys, pk.stt, pk.g, pk.perm, pk.pnow,
-                                            pk.tiles, h->sd->bnode.p, h->N, d, adj.p, *pods, st));
-            pk.on = false;
-        } else {
-            d.trace = h->trace_region(0);  // (the delta launch stays far below kTraceWgs workgroups at
-                                           // config 3; larger ones are not traced)
-            if ((pods ? pods->ntiles : 0) + (L + 1023) / 1024 > kTraceWgs) d.trace = nullptr;
-            HIPTRY(h, launch_hot_count_delta(h->sd->bnode.p, h->N, d, adj.p, st, pods));
-        }
-        if (pods_done) *pods_done = pods != nullptr && pods->P > 0;
-        h->delta_first = true;
-        h->delta_chunks = (L + kStepOneDeltaChunk - 1) / kStepOneDeltaChunk;
-    }
-    h->dl_adj_dirty[ab] = true;  // (until the node pass reads and zeroes the adjustments)
-    h->dl_pending = true;
-    *done = true;
-    return CRANE_OK;
-}
+// A binding-log refresh in two parts.  refresh_plan is the host's: the windows' cutoffs, the state
+// flags, a time-ordered log's suffix search and, where the delta form applies (kernels.hpp HotDelta),
+// the changed bindings and the adjustment buffer they go to — and which form counts:
+//   kDelta     counts = the anchor's dense counts + the changed bindings' adjustments
+//   kReanchor  the first refresh after the log or the node count changed, or one whose changed
+//              bindings pass half the widest window's suffix: the large form writes its dense
+//              counts as the new anchor (adjustments zero)
+//   kZero      no binding inside any window: every count is zero — K1 reads the (clean)
+//              adjustments as the anchor too; the anchor itself is kept for the next refresh
+//   kOther     the delta form does not apply: the dedupe, large or atomics form
+// refresh_launch launches that form, alone.  A step on a dispatch queue plans, then chooses its
+// first launch itself (crane_dyn_step_keys_queue): kDelta can share one with the stages pending.
+enum class Refresh { kOther, kZero, kReanchor, kDelta };
+struct RefreshPlan {
+    Refresh kind = Refresh::kOther;
+    HotCutoffs cut{};              // the windows' cutoffs, ascending
+    bool by_pos = false;           // a time-ordered log: bn / Bk are the widest window's suffix and pcut
+    HotCutoffs pcut{};             // ranks a binding by its position in it
+    const int32_t* bn = nullptr;   // the bindings the counting forms read
+    int64_t Bk = 0;
+    HotDelta d{};                  // kDelta: the changed positions,
+    int64_t L = 0;                 // how many,
+    uint32_t* adj = nullptr;       // and the adjustment buffer of this refresh (kZero, kReanchor: left clean)
+    HotPart gl{};                  // kReanchor: the large form's geometry over the suffix
+};
 
-// pods (optional): the step path's pod preparation, launched together with K2x
-// when the dedupe K2 runs (*pods_done reports whether it did).
-static int hot_values_locked(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, hipStream_t st,
-                             const PodPrep* pods = nullptr, bool* pods_done = nullptr) {
-    if (pods_done) *pods_done = false;
-    h->delta_first = false;
-    h->reset_deferred = false;
+static int refresh_plan(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, hipStream_t st, RefreshPlan& rp) {
+    rp = RefreshPlan{};
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before refreshing hot values");
     DevPolicy& dp = h->dp;
-    HotCutoffs cut{};
-    cut.n_win = dp.n_win;
+    const int nw = dp.n_win;
+    HotCutoffs& cut = rp.cut;
+    cut.n_win = nw;
     // time.Now().UTC().Unix() - int64(timeRange.Seconds())   (binding.go:85)
     const int64_t now_unix = floor_div(now_ns, 1000000000LL);
     int64_t c[kMaxWin];
     int order[kMaxWin];
-    for (int w = 0; w < dp.n_win; ++w) {
+    for (int w = 0; w < nw; ++w) {
         const int64_t trs = go_seconds_trunc(h->hot_tr[w]);
         c[w] = now_unix - trs;
         order[w] = w;
     }
-    std::stable_sort(order, order + dp.n_win, [&](int a, int b) { return c[a] < c[b]; });
-    for (int r = 0; r < dp.n_win; ++r) {
+    std::stable_sort(order, order + nw, [&](int a, int b) { return c[a] < c[b]; });
+    for (int r = 0; r < nw; ++r) {
         cut.sorted[r] = c[order[r]];
         dp.win_pos[order[r]] = r;
         dp.win_cut_sorted[r] = c[order[r]];
@@ -709,39 +591,129 @@ static int hot_values_locked(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, hip
     // then read only the node ids of the widest window's suffix and rank a binding by its
     // position — the same counts as the timestamp test, without the 8-byte stamps and without
     // the bindings older than every window.
-    const int32_t* bn = h->sd->bnode.p;
-    int64_t Bk = h->B;
-    HotCutoffs pcut = cut;
-    const bool by_pos = h->log_sorted && h->opt.k2_sorted && dp.n_win > 0 && (int64_t)h->sd->hts_copy.size() == h->B;
-    if (by_pos) {
-        // (the cutoffs move once per second: the last search's suffixes are reused until they do)
-        if (!h->pos_valid || std::memcmp(h->pos_cut, cut.sorted, sizeof(int64_t) * dp.n_win) != 0) {
-            // (a batch whose time advanced moves them: the sampled stamps narrow each search to one
-            // 64-stamp run, ~7 + 6 probes, instead of 20 probes across the 8 MB stamp array)
-            const std::vector<int64_t>& smp = h->sd->hts_sample;
-            const int64_t* t0 = h->sd->hts_copy.data();
-            for (int r = 0; r < dp.n_win; ++r) {
-                const int64_t j = std::upper_bound(smp.begin(), smp.end(), cut.sorted[r]) - smp.begin();
-                const int64_t lo = j == 0 ? 0 : 64 * (j - 1), hi = std::min<int64_t>(h->B, 64 * j);
-                h->pos_s[r] = std::upper_bound(t0 + lo, t0 + hi, cut.sorted[r]) - t0;
-            }
-            std::memcpy(h->pos_cut, cut.sorted, sizeof(int64_t) * dp.n_win);
-            h->pos_valid = true;
+    rp.bn = h->sd->bnode.p;
+    rp.Bk = h->B;
+    rp.pcut = cut;
+    rp.by_pos = h->log_sorted && h->opt.k2_sorted && nw > 0 && (int64_t)h->sd->hts_copy.size() == h->B;
+    if (!rp.by_pos) return CRANE_OK;
+    // (the cutoffs move once per second: the last search's suffixes are reused until they do)
+    if (!h->pos_valid || std::memcmp(h->pos_cut, cut.sorted, sizeof(int64_t) * nw) != 0) {
+        // (a batch whose time advanced moves them: the sampled stamps narrow each search to one
+        // 64-stamp run, ~7 + 6 probes, instead of 20 probes across the 8 MB stamp array)
+        const std::vector<int64_t>& smp = h->sd->hts_sample;
+        const int64_t* t0 = h->sd->hts_copy.data();
+        for (int r = 0; r < nw; ++r) {
+            const int64_t j = std::upper_bound(smp.begin(), smp.end(), cut.sorted[r]) - smp.begin();
+            const int64_t lo = j == 0 ? 0 : 64 * (j - 1), hi = std::min<int64_t>(h->B, 64 * j);
+            h->pos_s[r] = std::upper_bound(t0 + lo, t0 + hi, cut.sorted[r]) - t0;
         }
-        const int64_t s0 = h->pos_s[0];
-        for (int r = 0; r < dp.n_win; ++r) pcut.sorted[r] = h->pos_s[r] - s0 - 1;
-        pcut.by_pos = 1;
-        bn = h->sd->bnode.p + s0;
-        Bk = h->B - s0;
+        std::memcpy(h->pos_cut, cut.sorted, sizeof(int64_t) * nw);
+        h->pos_valid = true;
     }
-    if (by_pos && h->opt.k2_delta && h->opt.k2_form == 0) {
-        bool done = false;
-        const int rc = hot_delta_locked(h, Bk, pcut, st, pods, pods_done, &done);
-        if (rc || done) return rc;
+    const int64_t s0 = h->pos_s[0];
+    for (int r = 0; r < nw; ++r) rp.pcut.sorted[r] = h->pos_s[r] - s0 - 1;
+    rp.pcut.by_pos = 1;
+    rp.bn = h->sd->bnode.p + s0;
+    rp.Bk = h->B - s0;
+    if (!h->opt.k2_delta || h->opt.k2_form != 0) return CRANE_OK;
+    if (h->N <= 0 || h->N >= (1LL << 27) || nw > kDeltaMaxWin) return CRANE_OK;
+    const size_t nb = (size_t)nw * (size_t)h->N;
+    const bool anchored = h->dl_valid && h->dl_log_ver == h->sd_log_ver && h->dl_N == h->N && h->dl_B == h->B;
+    // the changed positions: per window rank r, between the anchor's and this refresh's suffix
+    // starts; merged
+    HotDelta& d = rp.d;
+    d.n_win = nw;
+    if (anchored) {
+        std::pair<int64_t, int64_t> rg[kMaxWin];
+        int n = 0;
+        for (int r = 0; r < nw; ++r) {
+            d.a[r] = h->dl_pos[r];
+            d.p[r] = h->pos_s[r];
+            const int64_t lo = std::min(d.a[r], d.p[r]), hi = std::max(d.a[r], d.p[r]);
+            if (hi > lo) rg[n++] = {lo, hi};
+        }
+        std::sort(rg, rg + n);
+        int m = 0;
+        for (int i = 0; i < n; ++i) {
+            if (m > 0 && rg[i].first <= rg[m - 1].second) rg[m - 1].second = std::max(rg[m - 1].second, rg[i].second);
+            else rg[m++] = rg[i];
+        }
+        d.n_rng = m;
+        d.start[0] = 0;
+        for (int k = 0; k < m; ++k) {
+            d.lo[k] = rg[k].first;
+            d.start[k + 1] = d.start[k] + (rg[k].second - rg[k].first);
+        }
+        rp.L = d.start[m];
     }
-    if (h->pk1.on)  // (a pending K1 goes in front of any other form's launches)
-        if (int rc = flush_pending(h)) return rc;
-    HotPart gx = hot_dedupe_geometry(Bk, h->N, dp.n_win, kK1Block);
+    // (a pending K1 holds one adjustment buffer until its launch: this refresh takes the other)
+    const int held = h->pipe.held_adj();
+    const int ab = held >= 0 ? held ^ 1 : h->dl_cur;
+    h->dl_cur = ab;
+    // (step_defer 2: the other buffer too, up front, unless a pending K1 holds it — an allocation
+    // and a fill wait for the queue, and belong to an engine's first step, not its third)
+    for (int b : {ab, ab ^ 1}) {
+        if (b != ab && (h->opt.step_defer != 2 || !tl_aql || held >= 0)) break;
+        DevBuf<uint32_t>& x = h->dl_adj[b];
+        if (x.n < nb) {
+            HIPTRY(h, x.reserve(nb));
+            h->dl_adj_dirty[b] = true;
+        }
+        if (h->dl_adj_dirty[b]) {  // (an earlier refresh's adjustments no node pass consumed, or a new buffer)
+            if (int rc = zero_for(h, x.p, x.n, st)) return rc;
+            h->dl_adj_dirty[b] = false;
+        }
+    }
+    rp.adj = h->dl_adj[ab].p;
+    h->dl_zero = rp.Bk == 0;
+    if (rp.Bk == 0) {
+        rp.kind = Refresh::kZero;
+    } else if (!anchored || 2 * rp.L > rp.Bk) {
+        rp.gl = hot_large_geometry(rp.Bk, h->N, nw);
+        if (rp.gl.ok) rp.kind = Refresh::kReanchor;
+    } else {
+        rp.kind = Refresh::kDelta;
+    }
+    return CRANE_OK;
+}
+
+// A delta-form refresh (any kind but kOther) went out: its adjustments wait for a node pass
+static void refresh_counted(crane_dyn* h) {
+    h->dl_adj_dirty[h->dl_cur] = true;  // (until the node pass reads and zeroes the adjustments)
+    h->dl_pending = true;
+}
+
+// pods (optional): the step path's pod preparation, launched together with the delta form or
+// K2x when one of them runs (*pods_done is set when it did).
+static int refresh_launch(crane_dyn* h, const RefreshPlan& rp, hipStream_t st, const PodPrep* pods, bool* pods_done) {
+    const DevPolicy& dp = h->dp;
+    const HotCutoffs& cut = rp.by_pos ? rp.pcut : rp.cut;
+    const bool with_pods = pods != nullptr && pods->P > 0;
+    if (rp.kind == Refresh::kReanchor) {
+        const HotPart gf = hot_large_geometry(h->B, h->N, dp.n_win);
+        HIPTRY(h, h->dl_base.reserve((size_t)dp.n_win * (size_t)h->N));
+        h->dl_valid = false;
+        HIPTRY(h, h->k2_sorted.reserve(std::max(hot_dedupe_scratch(rp.gl), gf.ok ? hot_dedupe_scratch(gf) : 0)));
+        HIPTRY(h, launch_hot_count_large(rp.bn, h->sd->bts.p, rp.Bk, h->N, rp.pcut, rp.gl, h->k2_sorted.p, h->dl_base.p,
+                                         h->n_cu, st, kK2lThreads));
+        std::memcpy(h->dl_pos, h->pos_s, sizeof(int64_t) * dp.n_win);
+        h->dl_valid = true;
+        h->dl_log_ver = h->sd_log_ver;
+        h->dl_N = h->N;
+        h->dl_B = h->B;
+    } else if (rp.kind == Refresh::kDelta) {
+        HotDelta d = rp.d;
+        d.trace = h->trace_region(0);  // (the delta launch stays far below kTraceWgs workgroups at
+                                       // config 3; larger ones are not traced)
+        if ((pods ? pods->ntiles : 0) + (rp.L + 1023) / 1024 > kTraceWgs) d.trace = nullptr;
+        HIPTRY(h, launch_hot_count_delta(h->sd->bnode.p, h->N, d, rp.adj, st, pods));
+        if (pods_done) *pods_done = with_pods;
+    }
+    if (rp.kind != Refresh::kOther) {
+        refresh_counted(h);
+        return CRANE_OK;
+    }
+    HotPart gx = hot_dedupe_geometry(rp.Bk, h->N, dp.n_win, kK1Block);
     gx.trace = gx.nblk <= kTraceWgs ? h->trace_region(0) : nullptr;
     if (h->opt.k2_form == 0 && gx.ok) {
         // one launch (+ K3p); the node pass counts its own block's entries (no buckets).  The
@@ -750,9 +722,9 @@ static int hot_values_locked(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, hip
         // cost 30-55 us per batch when the batch times advanced
         const HotPart gf = hot_dedupe_geometry(h->B, h->N, dp.n_win, kK1Block);
         HIPTRY(h, h->k2_sorted.reserve(std::max(hot_dedupe_scratch(gx), gf.ok ? hot_dedupe_scratch(gf) : 0)));
-        HIPTRY(h, launch_hot_count_dedupe(bn, h->sd->bts.p, Bk, h->N, by_pos ? pcut : cut, gx, h->k2_sorted.p, st, pods,
+        HIPTRY(h, launch_hot_count_dedupe(rp.bn, h->sd->bts.p, rp.Bk, h->N, cut, gx, h->k2_sorted.p, st, pods,
                                           kK2xThreads));
-        if (pods_done) *pods_done = pods != nullptr && pods->P > 0;
+        if (pods_done) *pods_done = with_pods;
         h->hx_g = gx;
         h->hx_pending = true;
         return CRANE_OK;
@@ -760,33 +732,35 @@ static int hot_values_locked(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, hip
     const size_t nb = (size_t)std::max(1, dp.n_win) * (size_t)std::max<int64_t>(h->N, 1);
     if (nb > h->buckets.n) h->buckets_zero = false;
     HIPTRY(h, h->buckets.reserve(nb));
-    HotPart gl = hot_large_geometry(Bk, h->N, dp.n_win);
+    HotPart gl = hot_large_geometry(rp.Bk, h->N, dp.n_win);
     gl.trace = gl.nblk <= kTraceWgs ? h->trace_region(0) : nullptr;  // (stamps per region)
     if ((h->opt.k2_form == 0 || h->opt.k2_form == 3) && gl.ok) {
         // the region pass with coarse bins + the dense per-bin histogram: every bucket row
         // is rewritten, so nothing is zeroed before and K1 leaves them
         const HotPart gf = hot_large_geometry(h->B, h->N, dp.n_win);
         HIPTRY(h, h->k2_sorted.reserve(std::max(hot_dedupe_scratch(gl), gf.ok ? hot_dedupe_scratch(gf) : 0)));
-        HIPTRY(h, launch_hot_count_large(bn, h->sd->bts.p, Bk, h->N, by_pos ? pcut : cut, gl, h->k2_sorted.p,
-                                         h->buckets.p, h->n_cu, st, kK2lThreads));
+        HIPTRY(h, launch_hot_count_large(rp.bn, h->sd->bts.p, rp.Bk, h->N, cut, gl, h->k2_sorted.p, h->buckets.p,
+                                         h->n_cu, st, kK2lThreads));
         h->buckets_zero = false;
         h->buckets_dense = true;
         return CRANE_OK;
     }
     h->buckets_dense = false;
-    if (!h->buckets_zero && tl_aql) {
-        // (on a dispatch queue: a fill is no kernel here — after the queue's packets, on the engine
-        // stream, waited for)
-        HIPTRY(h, aql_wait(tl_aql));
-        HIPTRY(h, hipMemsetAsync(h->buckets.p, 0, nb * sizeof(uint32_t), h->stream));
-        HIPTRY(h, hipStreamSynchronize(h->stream));
-    } else if (!h->buckets_zero) {
-        HIPTRY(h, hipMemsetAsync(h->buckets.p, 0, nb * sizeof(uint32_t), st));
-    }
+    if (!h->buckets_zero)
+        if (int rc = zero_for(h, h->buckets.p, nb, st)) return rc;
     // the atomics form (any size; shards past the large form's caps)
-    HIPTRY(h, launch_hot_count(h->sd->bnode.p, h->sd->bts.p, h->B, h->N, cut, h->buckets.p, st));
+    HIPTRY(h, launch_hot_count(h->sd->bnode.p, h->sd->bts.p, h->B, h->N, rp.cut, h->buckets.p, st));
     h->buckets_zero = false;
     return CRANE_OK;
+}
+
+// The refresh of every caller but the step on a dispatch queue: nothing is pending here (Locked)
+static int hot_values_locked(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, hipStream_t st,
+                             const PodPrep* pods = nullptr, bool* pods_done = nullptr) {
+    if (pods_done) *pods_done = false;
+    RefreshPlan rp;
+    if (int rc = refresh_plan(h, now_ns, hv_ts_ns, st, rp)) return rc;
+    return refresh_launch(h, rp, st, pods, pods_done);
 }
 
 // K1's workgroup size: the dedupe-form K2 bins nodes by it
@@ -864,15 +838,14 @@ static int node_pass_locked(crane_dyn* h, hipStream_t st, uint32_t* cnt_out = nu
 
 // ---- keys-only step path (step.hip): K3p -> [K1 +] K3a -> K3s
 struct StepPlan {
-    StepGeometry g;
-    StepTables stt;
+    K3sBatch k3s;         // the batch's K3s stage: its geometry, tables, pod set and keys, filled here once
     bool fuse;  // K3a fused into the node pass (records stale)
     int64_t* batch;       // this step's time range (K3p folds it, K1 reads it)
     int64_t* batch_next;  // the other range: reset by K3p for the next step
-    int32_t* perm;        // this step's K3p outputs (one of three sets, by sbatch_par)
-    int64_t* pnow;
+    int32_t* perm;        // this step's K3p outputs (one of three sets, by sbatch_par), as K3p writes
+    int64_t* pnow;        // them (k3s reads the same)
     int64_t* tiles;
-    int tset;             // the table set stt points into
+    int tset;             // the table set k3s.st points into
 };
 
 static bool step_path_ok(const crane_dyn* h, int64_t P) {
@@ -880,14 +853,13 @@ static bool step_path_ok(const crane_dyn* h, int64_t P) {
 }
 
 // tset: the table set (a step that leaves its K1 pending takes the set the pending K3s does not read)
-static int step_plan(crane_dyn* h, int64_t P, StepPlan& sp, int tset = 0) {
+static int step_plan(crane_dyn* h, int64_t P, long long* keys, StepPlan& sp, int tset = 0) {
     sp.fuse = h->rec_dirty;
     sp.tset = tset;
     crane_dyn::TabSet& tb = h->tab[tset];
     const int32_t bs = sp.fuse ? k1_bs(h) : kStepSeg;  // producer workgroup size
     const int32_t nblk = (int32_t)((h->N + bs - 1) / bs);
-    sp.g = step_geometry(P, h->N, nblk, 0);
-    const StepGeometry& g = sp.g;
+    const StepGeometry g = step_geometry(P, h->N, nblk, 0);
     for (int k = 0; k < 3; ++k) {
         HIPTRY(h, h->sperm[k].reserve((size_t)(g.ntiles * 1024)));
         HIPTRY(h, h->stile[k].reserve((size_t)(kTileStat * g.ntiles)));
@@ -919,8 +891,7 @@ static int step_plan(crane_dyn* h, int64_t P, StepPlan& sp, int tset = 0) {
     HIPTRY(h, tb.spm1.reserve((size_t)(2 * s1pad)));
     HIPTRY(h, tb.ssm0.reserve((size_t)(2 * s1pad)));
     HIPTRY(h, tb.smid.reserve((size_t)(2 * mpad)));
-    StepTables& t = sp.stt;
-    t = StepTables{};
+    StepTables t{};
     t.cnt = tb.scnt.p;
     t.flat = tb.scnt.p + (size_t)nblk * 4;
     t.single = tb.sstep1.p;
@@ -949,6 +920,7 @@ static int step_plan(crane_dyn* h, int64_t P, StepPlan& sp, int tset = 0) {
         }
     }
     t.trace = g.ngroups * g.R <= kTraceWgs ? h->trace_region(2) : nullptr;
+    sp.k3s = K3sBatch{h->N, h->node_offset, P, keys, t, g, sp.perm, sp.pnow, sp.tiles};
     return CRANE_OK;
 }
 
@@ -957,110 +929,109 @@ static void pods_ran(crane_dyn* h, int64_t P) {
     if (P > 0) h->sbatch_par = (h->sbatch_par + 1) % 3;
 }
 
-static int step_pods(crane_dyn* h, const StepPlan& sp, int64_t P, const int64_t* d_now, const uint8_t* d_flags,
-                     long long* d_keys, hipStream_t st) {
-    HIPTRY(h, launch_step_pods(d_now, d_flags, P, d_keys, sp.batch, sp.batch_next, sp.g, sp.perm, sp.pnow, sp.tiles,
-                               st));
-    pods_ran(h, P);
+// K3p's arguments (alone, or inside the refresh's launch)
+static PodPrep pod_prep(const StepPlan& sp, const int64_t* d_now, const uint8_t* d_flags) {
+    return PodPrep{d_now, d_flags, sp.k3s.P, sp.k3s.g.ntiles, sp.perm, sp.pnow, sp.tiles, sp.k3s.keys, sp.batch,
+                   sp.batch_next};
+}
+
+static int step_pods(crane_dyn* h, const StepPlan& sp, const int64_t* d_now, const uint8_t* d_flags, hipStream_t st) {
+    HIPTRY(h, launch_step_pods(d_now, d_flags, sp.k3s.P, sp.k3s.keys, sp.batch, sp.batch_next, sp.k3s.g, sp.perm,
+                               sp.pnow, sp.tiles, st));
+    pods_ran(h, sp.k3s.P);
     return CRANE_OK;
 }
 
-// defer 1: K3s left to the next step's launch (PendK3s); 2: K1 too (PendK1; the caller checked
-// that the streamed pass would run); reset: K3p left the keys' reset to K1's launch
-static int step_rest(crane_dyn* h, const StepPlan& sp, int64_t P, long long* d_keys, hipStream_t st,
-                     int defer = 0, bool reset = false) {
-    if (P == 0) return CRANE_OK;
-    crane_dyn::PendK3s nx;
-    nx.on = true;
-    nx.q = tl_aql;
-    nx.stt = sp.stt;
-    nx.g = sp.g;
-    nx.perm = sp.perm;
-    nx.pnow = sp.pnow;
-    nx.tiles = sp.tiles;
-    nx.P = P;
-    nx.keys = d_keys;
-    nx.tset = sp.tset;
-    nx.N = h->N;
+// defer 1: K3s left to the next step's launch (the pipe's k3s); 2: K1 too (the pipe's k1; the caller
+// checked that the streamed pass would run); reset: K3p left the keys' reset to K1's launch
+static int step_rest(crane_dyn* h, const StepPlan& sp, hipStream_t st, int defer = 0, bool reset = false) {
+    const K3sBatch& b = sp.k3s;
+    if (b.P == 0) return CRANE_OK;
+    crane_dyn::StepPipe& pipe = h->pipe;
+    if (defer) pipe.q = tl_aql;
     if (sp.fuse) {
         // (the records the fused step leaves stale serve as the streamed pass's scratch)
-        const K1Step ks{sp.tiles, sp.batch, (int32_t)sp.g.ntiles, h->dp.noprio, h->dp.wsum, h->dp.winv, sp.stt,
+        const K1Step ks{sp.tiles, sp.batch, (int32_t)b.g.ntiles, h->dp.noprio, h->dp.wsum, h->dp.winv, b.st,
                         h->rec.p, h->opt.k1_tail};
         if (defer == 2) {
             // planned now, with the state it would have found and leaves; launched with the next step
-            crane_dyn::PendK1& k1 = h->pk1;
+            crane_dyn::StepPipe::K1& k1 = pipe.k1;
             bool consume = false;
             const int adj = h->dl_cur;
             if (int rc = k1_args(h, k1.a, nullptr, &ks, &consume)) return rc;
             k1_launched(h, consume, false);
             k1.on = true;
-            k1.q = tl_aql;
             k1.ks = ks;
-            k1.next = nx;
+            k1.next = {true, b, sp.tset};
             k1.reset = reset;
             k1.adj = adj;
             return CRANE_OK;
         }
-        if (reset) HIPTRY(h, launch_keys_reset(d_keys, P, st));
+        if (reset) HIPTRY(h, launch_keys_reset(b.keys, b.P, st));
         int rc = node_pass_locked(h, st, nullptr, &ks);
         if (rc) return rc;
     } else {
-        if (reset) HIPTRY(h, launch_keys_reset(d_keys, P, st));
+        if (reset) HIPTRY(h, launch_keys_reset(b.keys, b.P, st));
         if (h->rec_dirty) {
             int rc = node_pass_locked(h, st);
             if (rc) return rc;
         }
-        HIPTRY(h, launch_step_nodes(h->shape, h->rec.p, h->N, h->dp.wsum, h->dp.noprio, sp.stt, sp.g, sp.tiles, st));
+        HIPTRY(h, launch_step_nodes(h->shape, h->rec.p, h->N, h->dp.wsum, h->dp.noprio, b.st, b.g, sp.tiles, st));
     }
-    if (defer) {  // (the next step's first launch runs it: PendK3s)
-        h->pend = nx;
+    if (defer) {  // (the next step's first launch runs it)
+        pipe.k3s = {true, b, sp.tset};
         return CRANE_OK;
     }
-    HIPTRY(h, launch_step_pairs(h->shape, h->N, h->node_offset, P, d_keys, sp.stt, sp.g, sp.perm, sp.pnow, sp.tiles, st));
+    HIPTRY(h, launch_step_pairs(b, st));
     return CRANE_OK;
 }
 
-// option step_defer: what the last steps left pending, launched now on its queue, in order, and
-// committed: the older batch's K3s (beside the pending K1, when there is one: one launch, which
-// also resets that K1's batch's keys if its K3p left that to it), then that batch's K3s
+// The pending stages as a one-launch step (kernels.hpp StepOne): the older batch's K3s, when there is
+// one, beside the pending K1, which also resets its own batch's keys if its K3p left that to it;
+// with rp, a step's delta form and K3p too, else nothing more (a flush).  The result points into
+// the pipe: launch it before the pipe advances.
+static StepOne pipe_step_one(const crane_dyn* h, const RefreshPlan* rp = nullptr, const PodPrep* pods = nullptr) {
+    const crane_dyn::StepPipe& pipe = h->pipe;
+    StepOne s{};
+    s.k3s = pipe.k3s.on ? &pipe.k3s.b : nullptr;
+    s.k1 = &pipe.k1.a;
+    s.ks = &pipe.k1.ks;
+    s.reset_keys = pipe.k1.reset ? pipe.k1.next.b.keys : nullptr;
+    s.reset_P = pipe.k1.next.b.P;
+    s.N = h->N;
+    if (rp) {
+        s.bnode = h->sd->bnode.p;
+        s.d = &rp->d;
+        s.adj = rp->adj;
+        s.pods = pods;
+    }
+    return s;
+}
+
+// Is a one-launch step with these parts resident at once (step.hip step_one_launch)?  One that is
+// not — a time jump's many changed bindings — keeps its launches apart.
+static bool step_one_resident(const crane_dyn* h, const K3sBatch* k3s, int64_t ntiles, int64_t delta_len) {
+    return step_one_workgroups(k3s ? k3s->g.ngroups * k3s->g.R : 0, h->N, ntiles, delta_len) <=
+           (int64_t)kStepOneWgPerCu * h->n_cu;
+}
+
+// option step_defer: what the pipe holds, launched now on its queue, in order, and committed: the
+// pending K1 with the older batch's K3s beside it, then that K1's batch's K3s
 namespace {
 int flush_pending(crane_dyn* h) {
-    crane_dyn::PendK3s& pk = h->pend;
-    crane_dyn::PendK1& k1 = h->pk1;
-    if (!pk.on && !k1.on) return CRANE_OK;
-    crane_queue* const q = k1.on ? k1.q : pk.q;
+    crane_dyn::StepPipe& pipe = h->pipe;
+    if (!pipe.any()) return CRANE_OK;
+    crane_queue* const q = pipe.queue();
     crane_queue* const prev = tl_aql;
     tl_aql = q;
     hipError_t e = hipSuccess;
-    if (k1.on) {
-        if (pk.on || k1.reset) {
-            StepOne s{};
-            s.N = h->N;
-            s.node_offset = h->node_offset;
-            if (pk.on) {
-                s.P_k3s = pk.P;
-                s.keys_k3s = pk.keys;
-                s.st = pk.stt;
-                s.g = pk.g;
-                s.perm = pk.perm;
-                s.pnow = pk.pnow;
-                s.tile_mm = pk.tiles;
-            }
-            s.k1 = &k1.a;
-            s.ks = &k1.ks;
-            s.reset_keys = k1.reset ? k1.next.keys : nullptr;
-            s.reset_P = k1.next.P;
-            e = launch_step_one(s, h->stream);
-        } else {
-            e = launch_node_pass(h->shape, k1.a, h->stream, &k1.ks, 1);
-        }
-        pk = k1.next;
-        k1.on = false;
+    if (pipe.k1.on) {
+        if (pipe.k3s.on || pipe.k1.reset) e = launch_step_one(pipe_step_one(h), h->stream);
+        else e = launch_node_pass(h->shape, pipe.k1.a, h->stream, &pipe.k1.ks, 1);
+        pipe.advance();
     }
-    if (e == hipSuccess && pk.on)
-        e = launch_step_pairs(h->shape, h->N, h->node_offset, pk.P, pk.keys, pk.stt, pk.g, pk.perm, pk.pnow, pk.tiles,
-                              h->stream);
-    pk.on = false;
+    if (e == hipSuccess && pipe.k3s.on) e = launch_step_pairs(pipe.k3s.b, h->stream);
+    pipe.k3s.on = false;
     const hipError_t c = aql_commit(q);
     tl_aql = prev;
     if (e != hipSuccess) return h->hipfail(e, "deferred step stages");
@@ -1101,9 +1072,9 @@ static int keys_locked(crane_dyn* h, int64_t P, const int64_t* d_now, const uint
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before evaluating pods");
     if (step_path_ok(h, P)) {
         StepPlan sp;
-        int rc = step_plan(h, P, sp);
-        if (!rc) rc = step_pods(h, sp, P, d_now, d_flags, d_keys, st);
-        if (!rc) rc = step_rest(h, sp, P, d_keys, st);
+        int rc = step_plan(h, P, d_keys, sp);
+        if (!rc) rc = step_pods(h, sp, d_now, d_flags, st);
+        if (!rc) rc = step_rest(h, sp, st);
         return rc;
     }
     return matrix_locked(h, P, d_now, d_flags, d_keys, nullptr, nullptr, false, 0, st);
@@ -1174,10 +1145,10 @@ int crane::engine_share_shard(crane_dyn* h, crane_dyn* from) {
 // a queue being destroyed hands itself back (aql.cpp; it has waited for its steps)
 void crane::engine_drop_queue(crane_dyn* h, crane_queue* q) {
     std::lock_guard<std::mutex> g(h->mu);
-    if ((h->pend.on && h->pend.q == q) || (h->pk1.on && h->pk1.q == q)) {
+    if (h->pipe.any() && h->pipe.queue() == q) {
         // (stages left pending on a queue going away run now: the engine's state says they did)
         if (flush_pending(h) == CRANE_OK) (void)aql_wait(q);
-        h->pend.on = h->pk1.on = false;
+        h->pipe.k3s.on = h->pipe.k1.on = false;
     }
     h->busy_q.erase(std::remove(h->busy_q.begin(), h->busy_q.end(), q), h->busy_q.end());
     h->seen_q.erase(std::remove(h->seen_q.begin(), h->seen_q.end(), q), h->seen_q.end());
@@ -1282,14 +1253,14 @@ int crane_dyn_forget_stream(crane_dyn* h, void* stream) {
 
 int crane_dyn_step_flush(crane_dyn* h) {
     if (!h) return CRANE_E_INVALID;
-    Locked lk(h);  // (runs a deferred K3s)
+    Locked lk(h);  // (runs what the pipe holds)
     return lk.rc;
 }
 
 int crane_dyn_forget_queue(crane_dyn* h, crane_queue* q) {
     if (!h) return CRANE_E_INVALID;
     std::lock_guard<std::mutex> g(h->mu);
-    if ((h->pend.on && h->pend.q == q) || (h->pk1.on && h->pk1.q == q))
+    if (h->pipe.any() && h->pipe.queue() == q)
         if (int rc = flush_pending(h)) return rc;
     auto sq = std::find(h->seen_q.begin(), h->seen_q.end(), q);
     if (sq != h->seen_q.end()) {
@@ -1698,14 +1669,14 @@ int crane_dyn_step_keys_async(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, in
     // K2x's launch when the dedupe K2 runs
     h->rec_dirty = true;
     StepPlan sp;
-    int rc = step_plan(h, P, sp);
+    int rc = step_plan(h, P, keys, sp);
     if (rc) return rc;
-    const PodPrep pp{d_now, d_flags, P, sp.g.ntiles, sp.perm, sp.pnow, sp.tiles, keys, sp.batch, sp.batch_next};
+    const PodPrep pp = pod_prep(sp, d_now, d_flags);
     bool pods_done = false;
     rc = hot_values_locked(h, now_ns, hv_ts_ns, st, &pp, &pods_done);
     if (pods_done) pods_ran(h, P);
-    if (!rc && !pods_done) rc = step_pods(h, sp, P, d_now, d_flags, keys, st);
-    if (!rc) rc = step_rest(h, sp, P, keys, st);
+    if (!rc && !pods_done) rc = step_pods(h, sp, d_now, d_flags, st);
+    if (!rc) rc = step_rest(h, sp, st);
     return rc ? rc : mark_busy(h, st);
 }
 
@@ -1724,7 +1695,10 @@ int crane_dyn_step_keys_queue(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, in
     }
     long long* keys = reinterpret_cast<long long*>(d_keys);
     if (!step_path_ok(h, P) || P == 0) {
-        // (the per-pair form has fills and copies: on the engine stream after the queue, waited for)
+        // (the per-pair form has fills and copies: on the engine stream after the queue, waited for
+        // — with what was pending on it, which no launch here takes in and whose K1 reads the
+        // anchor and the adjustments this refresh may rewrite)
+        if (int rc = flush_pending(h)) return rc;
         if (aql_wait(q) != hipSuccess) return h->fail(CRANE_E_HIP, std::string("queue: ") + aql_error(q));
         int rc = hot_values_locked(h, now_ns, hv_ts_ns, h->stream);
         if (!rc) rc = keys_locked(h, P, d_now, d_flags, keys, h->stream);
@@ -1739,58 +1713,83 @@ int crane_dyn_step_keys_queue(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, in
     {
         OnQueue on(q);
         const int defer = h->opt.step_defer;
-        crane_dyn::PendK3s& pk = h->pend;
-        crane_dyn::PendK1& k1 = h->pk1;
+        crane_dyn::StepPipe& pipe = h->pipe;
+        auto hip = [h](hipError_t e, const char* what) { return e == hipSuccess ? CRANE_OK : h->hipfail(e, what); };
         // What is pending runs first, alone: stages of another queue; a K3s writing the keys this
         // step writes (its K3p resets them) unless a pending K1 follows it (then this step, as
         // one launch, leaves the reset to the next: two buffers in alternation never drain); the
         // same keys on consecutive steps; stages planned for another batch size or node count (the
         // plan below may reallocate buffers they point into)
-        h->defer_reset = false;
-        if (pk.on || k1.on) {
-            crane_queue* const pq = k1.on ? k1.q : pk.q;
-            const int64_t pP = k1.on ? k1.next.P : pk.P;
-            const int64_t pN = k1.on ? k1.next.N : pk.N;
-            bool drain = pq != q || !defer || pP != P || pN != h->N || (pk.on && pk.P != P);
-            if (k1.on) drain = drain || k1.next.keys == keys;
-            else drain = drain || pk.keys == keys;
+        bool late_reset = false;  // this step's keys are what the pending K3s still merges into: if the
+                                  // step goes out as one launch, its K3p leaves their reset to the next
+        if (pipe.any()) {
+            const K3sBatch& last = pipe.last();
+            const bool drain = pipe.queue() != q || !defer || last.P != P || last.N != h->N ||
+                               (pipe.k3s.on && pipe.k3s.b.P != P) || last.keys == keys;
             if (drain) rc = flush_pending(h);
-            else h->defer_reset = k1.on && pk.on && pk.keys == keys;
+            else late_reset = pipe.k1.on && pipe.k3s.on && pipe.k3s.b.keys == keys;
         }
         h->rec_dirty = true;
         StepPlan sp{};
         // (the table set a pending stage does not hold: its K3s reads it after this step's K1 is planned)
-        const int tset = k1.on ? k1.next.tset ^ 1 : pk.on ? pk.tset ^ 1 : 0;
+        const int tset = pipe.free_tset();
         // (both table sets from the first step on, where the one-launch form can apply at all:
         // an allocation waits for the device)
-        if (!rc && defer == 2 && !k1.on && !pk.on && step_one_has(h->shape) && h->opt.k1_stream &&
+        if (!rc && defer == 2 && !pipe.any() && step_one_has(h->shape) && h->opt.k1_stream &&
             (h->N + kK1Block - 1) / kK1Block <= (int64_t)kStepOneWgPerCu * h->n_cu)
-            rc = step_plan(h, P, sp, 1);
-        if (!rc) rc = step_plan(h, P, sp, defer == 2 ? tset : 0);
-        const PodPrep pp{d_now, d_flags, P, sp.g.ntiles, sp.perm, sp.pnow, sp.tiles, keys, sp.batch, sp.batch_next};
-        bool pods_done = false;
-        if (!rc) rc = hot_values_locked(h, now_ns, hv_ts_ns, h->stream, &pp, &pods_done);
-        if (pods_done) pods_ran(h, P);
-        const bool reset = h->reset_deferred;
-        h->defer_reset = h->reset_deferred = false;
-        // (not taken into the first launch: before this step's node pass rewrites its tables)
-        if (!rc && (pk.on || k1.on) && !(h->delta_first && pk.on && !k1.on && pk.tset != sp.tset))
+            rc = step_plan(h, P, keys, sp, 1);
+        if (!rc) rc = step_plan(h, P, keys, sp, defer == 2 ? tset : 0);
+        const PodPrep pp = pod_prep(sp, d_now, d_flags);
+        RefreshPlan rp;
+        if (!rc) rc = refresh_plan(h, now_ns, hv_ts_ns, h->stream, rp);
+        // The first launch.  Only the delta form shares one with what is pending:
+        //   the pending K3s and K1 + the delta form + K3p: the whole step as one launch (step_defer 2);
+        //   the pending K3s + the delta form + K3p (step_defer 1, or a pipe that is filling);
+        //   the refresh's form + K3p where it takes it, alone.
+        // A pending K1 goes in front of every other form (the re-anchor rewrites the anchor it reads,
+        // and it belongs in front of this step's launches in any case), and in front of a delta
+        // launch that would not be resident at once: it is flushed, with the K3s beside it.
+        const bool delta = rp.kind == Refresh::kDelta;
+        if (!rc && pipe.k1.on &&
+            !(delta && step_one_resident(h, pipe.k3s.on ? &pipe.k3s.b : nullptr, sp.k3s.g.ntiles, rp.L)))
             rc = flush_pending(h);
-        if (!rc && !pods_done) rc = step_pods(h, sp, P, d_now, d_flags, keys, h->stream);
-        // step_defer 2 leaves K1 to the next launch when this step's first launch was the delta
-        // form's with K3p, the streamed 4 x 6 pass would run, and the one launch of a steady
-        // state (K3s + K1 + K3p + as many delta chunks as now) is resident at once; else as 1
+        bool pods_done = false, reset = false;
+        if (!rc && delta && pipe.k1.on) {
+            PodPrep p1 = pp;
+            if (late_reset) p1.keys = nullptr;
+            rc = hip(launch_step_one(pipe_step_one(h, &rp, &p1), h->stream), "launch_step_one");
+            if (!rc) pipe.advance();
+            reset = late_reset;
+        } else if (!rc && delta && pipe.k3s.on) {
+            rc = hip(launch_k3s_delta_pods(pipe.k3s.b, h->sd->bnode.p, h->N, rp.d, rp.adj, pp, h->stream),
+                     "launch_k3s_delta_pods");
+            if (!rc) pipe.k3s.on = false;
+        } else if (!rc) {
+            rc = refresh_launch(h, rp, h->stream, &pp, &pods_done);
+        }
+        if (!rc && delta && !pods_done) {  // (a shared launch went out: it held the delta form and K3p)
+            refresh_counted(h);
+            pods_done = true;
+        }
+        if (pods_done) pods_ran(h, P);
+        // A K3s not taken into the first launch runs now, before this step's node pass rewrites its
+        // tables (the one launch left the next K3s pending: it reads the other table set, unless
+        // the option changed under it)
+        if (!rc && pipe.any() && !(delta && pipe.k3s.tset != sp.tset)) rc = flush_pending(h);
+        if (!rc && !pods_done) rc = step_pods(h, sp, d_now, d_flags, h->stream);
+        // What this step leaves pending.  step_defer 2 leaves K1 to the next launch when this step's
+        // first launch held the delta form and K3p, the streamed 4 x 6 pass would run, and the one
+        // launch of a steady state (K3s + K1 + K3p + as many delta chunks as now) is resident at
+        // once; else as 1: K3s alone
         int dl = defer;
         if (defer == 2) {
             const bool stream_k1 = h->opt.k1_stream && sp.fuse && !h->hx_pending && k1_bs(h) == kK1Block &&
                                    step_one_has(h->shape) && h->N > 0;
-            const bool fits = step_one_workgroups(sp.g.ngroups * sp.g.R, h->N, sp.g.ntiles, 0) + h->delta_chunks <=
-                              (int64_t)kStepOneWgPerCu * h->n_cu;
-            if (!(h->delta_first && pods_done && !h->dl_zero && stream_k1 && fits)) dl = 1;
+            if (!(delta && pods_done && stream_k1 && step_one_resident(h, &sp.k3s, sp.k3s.g.ntiles, rp.L))) dl = 1;
         }
         // (a K3s still pending goes in front of a K1 launched now and of the K3s pending after it)
-        if (!rc && dl != 2 && pk.on) rc = flush_pending(h);
-        if (!rc) rc = step_rest(h, sp, P, keys, h->stream, dl, reset);
+        if (!rc && dl != 2 && pipe.k3s.on) rc = flush_pending(h);
+        if (!rc) rc = step_rest(h, sp, h->stream, dl, reset);
     }
     // (what was written runs even after an error: the packets before it are whole)
     const hipError_t ce = aql_commit(q);

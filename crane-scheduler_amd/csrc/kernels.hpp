@@ -333,12 +333,21 @@ struct StepGeometry {
 constexpr int kK3sMaxBlk = 256;  // producer blocks per K3s workgroup (one lane each)
 int step_breakpoints(int shape);  // in-range expiries per node and kind at most: PR + 2
 StepGeometry step_geometry(int64_t P, int64_t N, int32_t nblk, int32_t blk_per_wg = 0);
-// The previous step's K3s (launch_step_pairs' arguments) with this step's delta form + K3p in one
-// launch (step.hip k3s_delta_pods)
-hipError_t launch_k3s_delta_pods(int64_t N_k3s, int64_t node_offset, int64_t P_k3s, long long* keys_k3s,
-                                 const StepTables& st, const StepGeometry& g, const int32_t* perm, const int64_t* pnow,
-                                 const int64_t* tile_mm, const int32_t* bnode, int64_t N, const HotDelta& d,
-                                 uint32_t* adj, const PodPrep& pods, hipStream_t s);
+// One batch's K3s stage, as the step plan leaves it: the shard's nodes it was planned for, the pods'
+// keys it merges into, the step tables its producers (K1 / K3a) fill and K3p's outputs.  The one
+// description every K3s launch takes, alone or inside another launch, now or steps later.
+struct K3sBatch {
+    int64_t N, node_offset, P;
+    long long* keys;
+    StepTables st;
+    StepGeometry g;
+    const int32_t* perm;
+    const int64_t* pnow;
+    const int64_t* tile_mm;
+};
+// The previous step's K3s with this step's delta form + K3p in one launch (step.hip k3s_delta_pods)
+hipError_t launch_k3s_delta_pods(const K3sBatch& b, const int32_t* bnode, int64_t N, const HotDelta& d, uint32_t* adj,
+                                 const PodPrep& pods, hipStream_t s);
 struct K1Args;
 struct K1Step;
 // One step on a dispatch queue as one launch (step.hip step_one_launch): K3s of the batch two
@@ -346,18 +355,10 @@ struct K1Step;
 // by side.  The three work on different batches and share nothing within the launch: K3s reads
 // the tables and pod set K1 and K3p wrote two and one launches ago (the engine keeps two sets of
 // tables, three of pod sets, two of adjustments), and the keys K3s merges into are reset beside
-// the K1 of their own batch (reset_keys), one launch before.  Any part may be absent (P_k3s = 0,
+// the K1 of their own batch (reset_keys), one launch before.  Any part may be absent (k3s null,
 // k1 null, d null).  Instances: the 4 x 6 record shape (step_one_has).
 struct StepOne {
-    int64_t N, node_offset;
-    // K3s (launch_step_pairs' arguments)
-    int64_t P_k3s;
-    long long* keys_k3s;
-    StepTables st;
-    StepGeometry g;
-    const int32_t* perm;
-    const int64_t* pnow;
-    const int64_t* tile_mm;
+    const K3sBatch* k3s;  // null: no K3s
     // K1 (launch_stream_steps' arguments), and the keys its batch's K3s will merge into, reset
     // to -1 here (null: K3p did)
     const K1Args* k1;
@@ -366,6 +367,7 @@ struct StepOne {
     int64_t reset_P;
     // the delta form + K3p (launch_hot_count_delta's arguments)
     const int32_t* bnode;
+    int64_t N;
     const HotDelta* d;
     uint32_t* adj;
     const PodPrep* pods;
@@ -389,9 +391,7 @@ hipError_t launch_step_pods(const int64_t* now, const uint8_t* flags, int64_t P,
 hipError_t launch_step_nodes(int shape, const void* rec, int64_t N, double wsum, int32_t noprio,
                              const StepTables& st, const StepGeometry& g, const int64_t* tile_mm, hipStream_t s);
 // K3s: (pod, stepped node) pairs + flat maxima -> keys (after K3a or K1's STEP form)
-hipError_t launch_step_pairs(int shape, int64_t N, int64_t node_offset, int64_t P, long long* keys,
-                             const StepTables& st, const StepGeometry& g, const int32_t* perm, const int64_t* pnow,
-                             const int64_t* tile_mm, hipStream_t s);
+hipError_t launch_step_pairs(const K3sBatch& b, hipStream_t s);
 // K1's fused step form: the node pass also builds the step tables of a pod batch
 struct K1Step {
     const int64_t* tile_mm;  // K3p's per-tile stats (kTileStat)

@@ -752,14 +752,12 @@ hipError_t launch_step_nodes(int shape, const void* rec, int64_t N, double wsum,
     }
 }
 
-hipError_t launch_k3s_delta_pods(int64_t N_k3s, int64_t node_offset, int64_t P_k3s, long long* keys_k3s,
-                                 const StepTables& st, const StepGeometry& g, const int32_t* perm, const int64_t* pnow,
-                                 const int64_t* tile_mm, const int32_t* bnode, int64_t N, const HotDelta& d,
-                                 uint32_t* adj, const PodPrep& pods, hipStream_t s) {
-    if (P_k3s <= 0 || N_k3s <= 0 || d.n_win < 1 || d.n_win > kDeltaMaxWin || d.n_rng < 0 || d.n_rng > kMaxWin ||
+hipError_t launch_k3s_delta_pods(const K3sBatch& b, const int32_t* bnode, int64_t N, const HotDelta& d, uint32_t* adj,
+                                 const PodPrep& pods, hipStream_t s) {
+    if (b.P <= 0 || b.N <= 0 || d.n_win < 1 || d.n_win > kDeltaMaxWin || d.n_rng < 0 || d.n_rng > kMaxWin ||
         N >= (1LL << 27))
         return hipErrorInvalidValue;
-    const int64_t nk = g.ngroups * g.R;
+    const int64_t nk = b.g.ngroups * b.g.R;
     const int64_t L = d.n_rng > 0 ? d.start[d.n_rng] : 0;
     const int64_t grid = nk + (pods.P > 0 ? pods.ntiles : 0) + (L + kDeltaChunk - 1) / kDeltaChunk;
     if (grid >= (1LL << 31) || nk >= (1LL << 31)) return hipErrorInvalidValue;
@@ -770,7 +768,7 @@ hipError_t launch_k3s_delta_pods(int64_t N_k3s, int64_t node_offset, int64_t P_k
     static const hipError_t attr = hipFuncSetAttribute((const void*)k3s_delta_pods,
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (attr != hipSuccess) return attr;
-    const K3sArgs k{st, perm, pnow, tile_mm, P_k3s, node_offset, g.R, keys_k3s};
+    const K3sArgs k{b.st, b.perm, b.pnow, b.tile_mm, b.P, b.node_offset, b.g.R, b.keys};
     return klaunch("k3s_eval+k2_delta+k3p_pods", k3s_delta_pods, dim3((unsigned)grid), dim3(kK3sThreads), lds, s, k,
                    (int32_t)nk, bnode, N, d, adj, pp);
 }
@@ -785,13 +783,13 @@ int64_t step_one_workgroups(int64_t nk3s, int64_t N_k1, int64_t ntiles, int64_t 
 }
 
 hipError_t launch_step_one(const StepOne& s, hipStream_t st) {
-    const bool k3s = s.P_k3s > 0 && s.N > 0, k1 = s.k1 && s.ks && s.k1->N > 0;
+    const bool k3s = s.k3s && s.k3s->P > 0 && s.k3s->N > 0, k1 = s.k1 && s.ks && s.k1->N > 0;
     const bool delta = s.d != nullptr, pods = s.pods && s.pods->P > 0;
     if (delta && (s.d->n_win < 1 || s.d->n_win > kDeltaMaxWin || s.d->n_rng < 0 || s.d->n_rng > kMaxWin ||
                   s.N >= (1LL << 27)))
         return hipErrorInvalidValue;
     if (k1 && (s.k1->threads != 256 || s.k1->out || s.k1->hx_region || !s.ks->st.stage)) return hipErrorInvalidValue;
-    const int64_t nk = k3s ? s.g.ngroups * s.g.R : 0;
+    const int64_t nk = k3s ? s.k3s->g.ngroups * s.k3s->g.R : 0;
     const int64_t nk1 = k1 ? (s.k1->N + 255) / 256 : 0, nk1pad = (nk1 + 7) / 8 * 8;
     const int64_t L = delta && s.d->n_rng > 0 ? s.d->start[s.d->n_rng] : 0;
     const KeyReset kr{s.reset_keys, k1 && s.reset_keys && s.reset_P > 0 ? s.reset_P : 0};
@@ -800,7 +798,8 @@ hipError_t launch_step_one(const StepOne& s, hipStream_t st) {
                          (L + kStepOneDeltaChunk - 1) / kStepOneDeltaChunk;
     if (grid >= (1LL << 31)) return hipErrorInvalidValue;
     if (grid == 0) return hipSuccess;
-    const K3sArgs k{s.st, s.perm, s.pnow, s.tile_mm, k3s ? s.P_k3s : 0, s.node_offset, s.g.R, s.keys_k3s};
+    const K3sBatch kb = k3s ? *s.k3s : K3sBatch{};
+    const K3sArgs k{kb.st, kb.perm, kb.pnow, kb.tile_mm, kb.P, kb.node_offset, kb.g.R, kb.keys};
     const K1Args a = k1 ? *s.k1 : K1Args{};
     const K1Step ks = k1 ? *s.ks : K1Step{};
     const HotDelta d = delta ? *s.d : HotDelta{};
@@ -824,13 +823,11 @@ hipError_t launch_keys_reset(long long* keys, int64_t P, hipStream_t st) {
     return klaunch("keys_reset", keys_reset, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, keys, P);
 }
 
-hipError_t launch_step_pairs(int shape, int64_t N, int64_t node_offset, int64_t P, long long* keys,
-                             const StepTables& st, const StepGeometry& g, const int32_t* perm, const int64_t* pnow,
-                             const int64_t* tile_mm, hipStream_t s) {
-    (void)shape;
-    if (P <= 0 || N <= 0) return hipSuccess;
-    const dim3 grid((unsigned)(g.ngroups * g.R)), blk(kK3sThreads);
-    return klaunch("k3s_eval", k3s_eval, grid, blk, 0, s, st, perm, pnow, tile_mm, P, node_offset, g.R, keys);
+hipError_t launch_step_pairs(const K3sBatch& b, hipStream_t s) {
+    if (b.P <= 0 || b.N <= 0) return hipSuccess;
+    const dim3 grid((unsigned)(b.g.ngroups * b.g.R)), blk(kK3sThreads);
+    return klaunch("k3s_eval", k3s_eval, grid, blk, 0, s, b.st, b.perm, b.pnow, b.tile_mm, b.P, b.node_offset, b.g.R,
+                   b.keys);
 }
 
 }  // namespace crane

@@ -200,3 +200,63 @@ def test_pod_count_changes_across_a_tile(worlds, sizes, n_bind):
             assert torch.equal(bufs[b], w.ref(times[b], per[b])), f"batch {b} (P={per[b]})"
     eng.close()
     q.close()
+
+
+def test_time_jump_past_the_resident_launch(worlds):
+    """A step whose changed bindings pass what one resident launch holds (7 workgroups per compute
+    unit, 512 changed bindings per delta workgroup) keeps its launches apart: what is pending runs
+    first and the delta form goes out alone.  300 nodes, 257 pods; a time-ordered log uniform over
+    the 300 s of the widest window before the first batch, dense enough that batch 4's jump of 55 s
+    changes more than 7 * CUs * 512 bindings against the anchor (asserted, counted on the host)
+    while staying at most half the widest window's suffix (asserted: the step does not re-anchor);
+    the other batches are 1 s apart and back near the anchor.  Batch 4 writes more than one
+    packet, batches 2, 3 and 5 to 7 exactly one, and every batch equals the stream engine's."""
+    import torch
+    P, jump = 257, 55
+    base = worlds(300, BINDINGS[0])
+    limit = 7 * torch.cuda.get_device_properties(0).multi_processor_count * CHUNK
+    rate = -(-103 * limit // (100 * 2 * jump))  # bindings per second: 2 * jump * rate = 1.03 * limit
+    rng = np.random.default_rng(20261022)
+    t0s = T0 // 10**9
+    b_ts = np.sort(rng.integers(t0s - 300, t0s + 1, 300 * rate)).astype(np.int64)
+    b_node = rng.integers(0, 300, b_ts.size).astype(np.int32)
+    times = [T0 + s * 10**9 for s in (0, 1, 2, 3, jump, 1, 2, 3)]
+    changed = changed_bindings(base.spec, b_ts, times)
+    widest = max(tr for tr, _ in base.spec["hotValue"]) // 10**9
+    suffix = b_ts.size - int(np.searchsorted(b_ts, times[4] // 10**9 - widest, side="right"))
+    assert changed[4] > limit, (changed, limit)
+    assert 2 * changed[4] <= suffix, (changed, suffix)
+    assert max(changed[:4] + changed[5:]) < limit // 8, changed
+
+    def engine(opts=()):
+        e = cd.Engine(cd.Policy(base.spec), 0)
+        for k, v in opts:
+            e.set_option(k, v)
+        val, ts, _ = base.c.rows(e.metric_names)
+        e.upload_nodes(val, ts, base.c.hv, base.c.hv_ts)
+        e.upload_bindings(b_node, b_ts)
+        return e
+
+    ref_eng, eng = engine(), engine((("step_defer", 2),))
+    q = cd.Queue(0)
+    d_now = [base.now_dev(t, P) for t in times]
+    bufs = [torch.empty(P, dtype=torch.int64, device=base.dev) for _ in times]
+    refs = [torch.empty(P, dtype=torch.int64, device=base.dev) for _ in times]
+    torch.cuda.synchronize()
+    for b, t in enumerate(times):
+        ref_eng.step_keys_async(t, t, d_now[b], base.d_flags[:P], refs[b], base.st.cuda_stream)
+    base.st.synchronize()
+    packets = []
+    for b, t in enumerate(times):
+        before = q.packets()
+        eng.step_keys_queue(t, t, d_now[b], base.d_flags[:P], bufs[b], q)
+        packets.append(q.packets() - before)
+    eng.step_flush()
+    q.wait()
+    print(f"changed {changed} limit {limit} suffix {suffix} packets {packets}")
+    assert packets[4] > 1 and packets[2:4] == [1, 1] and packets[5:] == [1, 1, 1], packets
+    for b in range(len(times)):
+        assert torch.equal(bufs[b], refs[b]), f"batch {b}"
+    for e in (ref_eng, eng):
+        e.close()
+    q.close()

@@ -4,7 +4,8 @@ K3p, the previous batch's K1 and the K3s of the batch before, so two batches sta
 engine.  Every test compares a batch's keys bit for bit (torch.equal) with the same batch stepped
 by a second engine on a HIP stream (the path the oracle tests pin): through filling, steady state
 and draining of the pipeline, the key-buffer patterns, the first launches that cannot take the
-form, state changes and batch-size changes in between, and the group.
+form, state changes and batch-size changes in between, and the group.  Seven scenarios also pin the
+packets each step wrote (PARENT_PACKETS): which launches a step takes, not only what they compute.
 Shapes: 5,000 nodes = 20 K1 blocks (the last partial, >= 8 so K3s's XCD grouping is on), 1,500
 pods = two pod tiles (the second partial), 40,000 bindings, the default policy.
 Reference: plugins.go:39-98 + selectHost; binding.go:81-97."""
@@ -72,6 +73,25 @@ def _times(n):
     return [T0 + (k % 4) * STEP_NS for k in range(n)]
 
 
+# Packets written per step, recorded from the parent of the change that gathered the queue step's
+# pending state and launch choice in one place (commit b375471), on an MI355X: the literals are
+# that commit's, not the code under test's, so a drift in which launches a step takes fails here.
+PARENT_PACKETS = {
+    "fill_steady_drain_9": [4, 1, 1, 1, 1, 1, 1, 1, 1],
+    "same_buffer_twice_running": [4, 1, 1, 1, 1, 3, 1, 1, 1],
+    "other_first_launches_k2_form": [4, 5, 5, 5, 5, 5],
+    "other_first_launches_k2_delta": [2, 3, 3, 3, 3, 3],
+    "step_defer_1_two_alternating_buffers": [4, 2, 2, 2, 2, 2],
+    "reanchor_and_upload_between_steps": [4, 1, 1, 1, 6, 1, 4, 1, 4, 1],
+    "batch_size_changes_on_one_queue": [4, 1, 1, 3, 1, 1, 3, 1, 1, 3, 1],
+}
+
+
+def _pinned(name, packets):
+    print(f"packets[{name!r}] = {packets}")
+    assert packets == PARENT_PACKETS[name], (name, packets)
+
+
 def _run(w, eng, q, times, bufs, P=N_PODS, between=None):
     """Batch b at times[b] into bufs[b] on the queue; between(b) runs before batch b's step."""
     import torch
@@ -98,11 +118,13 @@ def test_fill_steady_drain(world, n):
     q = cd.Queue(0)
     times = _times(n)
     bufs = [torch.empty(N_PODS, dtype=torch.int64, device=w.dev) for _ in times]
-    _run(w, eng, q, times, bufs)
+    packets = _run(w, eng, q, times, bufs)
     eng.step_flush()
     q.wait()
     for b, t in enumerate(times):
         assert torch.equal(bufs[b], w.ref(t)), f"batch {b} of {n}"
+    if n == 9:
+        _pinned("fill_steady_drain_9", packets)
     eng.close()
     q.close()
 
@@ -138,12 +160,13 @@ def test_same_buffer_twice_running(world):
     times = _times(9)
     bufs = [torch.empty(N_PODS, dtype=torch.int64, device=w.dev) for _ in times]
     bufs[5] = bufs[4]
-    _run(w, eng, q, times, bufs)
+    packets = _run(w, eng, q, times, bufs)
     eng.step_flush()
     q.wait()
     for b, t in enumerate(times):
         if b != 4:
             assert torch.equal(bufs[b], w.ref(t)), f"batch {b}"
+    _pinned("same_buffer_twice_running", packets)
     eng.close()
     q.close()
 
@@ -157,11 +180,33 @@ def test_other_first_launches_fall_back(world, opts):
     q = cd.Queue(0)
     times = _times(6)
     bufs = [torch.empty(N_PODS, dtype=torch.int64, device=w.dev) for _ in times]
-    _run(w, eng, q, times, bufs)
+    packets = _run(w, eng, q, times, bufs)
     eng.step_flush()
     q.wait()
     for b, t in enumerate(times):
         assert torch.equal(bufs[b], w.ref(t)), f"batch {b}"
+    _pinned("other_first_launches_" + opts[0][0], packets)
+    eng.close()
+    q.close()
+
+
+def test_step_defer_1_two_alternating_buffers(world):
+    """Option step_defer 1 (a step leaves only its K3s to the next one's first launch): six batches
+    on one queue into two key buffers in alternation.  The last two batches' buffers equal the
+    reference, and the packets per step are the recorded ones."""
+    import torch
+    w = world
+    eng = _engine(w.spec, w.c, (("step_defer", 1),))
+    q = cd.Queue(0)
+    times = _times(6)
+    two = [torch.empty(N_PODS, dtype=torch.int64, device=w.dev) for _ in range(2)]
+    bufs = [two[b % 2] for b in range(6)]
+    packets = _run(w, eng, q, times, bufs)
+    eng.step_flush()
+    q.wait()
+    assert torch.equal(bufs[4], w.ref(times[4]))
+    assert torch.equal(bufs[5], w.ref(times[5]))
+    _pinned("step_defer_1_two_alternating_buffers", packets)
     eng.close()
     q.close()
 
@@ -185,11 +230,12 @@ def test_reanchor_and_upload_between_steps(world):
         if b == 8:
             val, ts, _ = w.c.rows(eng.metric_names)
             eng.upload_nodes(val, ts, w.c.hv, w.c.hv_ts)
-    _run(w, eng, q, times, bufs, between=between)
+    packets = _run(w, eng, q, times, bufs, between=between)
     eng.step_flush()
     q.wait()
     for b, t in enumerate(times):
         assert torch.equal(bufs[b], w.ref(t)), f"batch {b}"
+    _pinned("reanchor_and_upload_between_steps", packets)
     eng.close()
     q.close()
 
@@ -207,12 +253,16 @@ def test_batch_size_changes_on_one_queue(world):
     d_now = [w.now_dev(t, P) for t, P in zip(times, sizes)]
     bufs = [torch.empty(P, dtype=torch.int64, device=w.dev) for P in sizes]
     torch.cuda.synchronize()
+    packets = []
     for b, (t, P) in enumerate(zip(times, sizes)):
+        before = q.packets()
         eng.step_keys_queue(t, t, d_now[b], w.d_flags[:P], bufs[b], q)
+        packets.append(q.packets() - before)
     eng.step_flush()
     q.wait()
     for b, (t, P) in enumerate(zip(times, sizes)):
         assert torch.equal(bufs[b], w.ref(t, P)), f"batch {b} (P={P})"
+    _pinned("batch_size_changes_on_one_queue", packets)
     eng.close()
     q.close()
 
