@@ -92,8 +92,18 @@ __device__ __forceinline__ int32_t score_at_lds(int64_t t, const NodeRec<PD, PR>
 #ifndef K1S_SCAP
 #define K1S_SCAP 128
 #endif
+#ifndef K1S_RTAIL  // the register tail for blocks of few one-step records (A/B: 0 the generic tail always)
+#define K1S_RTAIL 1
+#endif
+#ifndef K1S_SMALL  // kSmallTail (A/B: 16; at most 32)
+#define K1S_SMALL 32
+#endif
 constexpr int kSRec = K1S_SREC;  // stepped records staged per chunk
 constexpr int kSCap = K1S_SCAP;  // one-step records per kind staged in LDS (more: st.stage)
+// one-step records per kind up to which a block takes the register tail (small_tail): one per
+// lane of a half wave (the other half takes the tile bounds), each lane walking all of them
+constexpr int kSmallTail = K1S_SMALL;
+static_assert(kSmallTail <= 32 && kSmallTail <= kSCap, "one record per lane of a half wave, staged in LDS");
 
 template <int PD, int PR>
 __device__ __forceinline__ void emit_task(const NodeRec<PD, PR>& r, int64_t n, int q, const int32_t* dw, int64_t tmin,
@@ -207,6 +217,63 @@ __device__ __forceinline__ void tail(bool g1, Rec* lrec, Step1* s1l, Step1* srt,
         step_pieces<BS>(ssh, step.st, blk, ps);
         if (g1) step_tile_rows<BS, kSCap, true>(s1l, srt, ssh, step.st, blk, &tpre, ps);
         else step_tile_rows<BS, kSCap, false>(s1l, srt, ssh, step.st, blk, &tpre, ps);
+    }
+    CRANE_TSTAMP(trace, wg, 4);
+}
+
+// The same epilogue for a block of at most kSmallTail one-step records per kind (n0 / n1, staged in
+// s1l) in a step without st.prow, in registers and wave-local (step_node.hpp small_scan): kind T
+// on wave T (the caller's waves 2 and 3 have left), or with ONE both kinds in turn on wave 0.
+// Lanes 0-31 are the kind's records, lanes 32-63 the bounds of the first 16 tiles (pre: loaded by
+// the caller before the emit, small_tail_bounds), so one scan gives the records' positions and
+// maxima and the rows; more tiles take further scans.  No barrier: the caller had one after the
+// emit; ssh.fm holds the per-wave flat maxima.  Nothing is stored before the last scan of round 0
+// (a wait for a later load would wait for the stores too).  Stamp 6 is wave 0's after its records
+// went out, 4 its end.
+// (small_tail_bounds: the first 16 tiles' bounds of this wave's kind, or with ONE of both kinds)
+template <bool ONE>
+__device__ __forceinline__ void small_tail_bounds(const StepTables& st, int64_t (&pre)[2]) {
+    const int lane = threadIdx.x & 63;
+    const int T0 = ONE ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    pre[0] = small_tile_bound(st, T0, 0, lane);
+    pre[1] = ONE ? small_tile_bound(st, 1, 0, lane) : 0;
+}
+template <bool ONE>
+__device__ __forceinline__ void small_tail(const Step1* s1l, int32_t n0, int32_t n1, const StepShared& ssh,
+                                           const K1Step& step, int64_t blk, const int64_t (&pre)[2], bool rows,
+                                           unsigned long long* trace, int64_t wg) {
+    constexpr int NK = ONE ? 2 : 1;
+    const StepTables& st = step.st;
+    const int lane = threadIdx.x & 63;
+    const int T0 = ONE ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int tl = lane < 32 ? lane : 64;  // ties: a record by slot, a bound takes every bp <= it
+    int32_t n[NK], fl[NK];
+    Step1 r[NK];
+    SmallScan sc[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+        const int T = T0 + k;
+        n[k] = __builtin_amdgcn_readfirstlane(T ? n1 : n0);
+        fl[k] = max(max(ssh.fm[T][0], ssh.fm[T][1]), max(ssh.fm[T][2], ssh.fm[T][3]));
+        r[k].bp = 0;
+        r[k].k0 = r[k].k1 = -1;
+        if (lane < n[k]) r[k] = s1l[T * kSCap + lane];
+    }
+#pragma unroll
+    for (int k = 0; k < NK; ++k) sc[k] = small_scan(r[k], n[k], lane < 32 ? r[k].bp : pre[k], tl);
+#pragma unroll
+    for (int k = 0; k < NK; ++k) small_records_store(T0 + k, n[k], r[k], sc[k], st, blk);
+    CRANE_TSTAMP(trace, wg, 6);
+    if (rows) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) small_row_store(T0 + k, 0, sc[k], fl[k], st, blk);
+        for (int t0 = 16; t0 < st.ntiles; t0 += 16) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const SmallScan s = small_scan(r[k], n[k], small_tile_bound(st, T0 + k, t0, lane), 64);
+                small_row_store(T0 + k, t0, s, fl[k], st, blk);
+            }
+        }
     }
     CRANE_TSTAMP(trace, wg, 4);
 }
@@ -465,6 +532,18 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
     const bool emit1 = t1 && nst * (PR + 2) <= 64;  // (workgroup-uniform)
     if (emit1 && threadIdx.x >= 64) return;
     const int nthr = emit1 ? 64 : BS;
+#if K1S_RTAIL
+    // few one-step records, staged in LDS, no elementary pieces (workgroup-uniform): the tail runs
+    // in registers (small_tail); its first tile bounds load now, behind the emit
+    const int32_t n0 = (int32_t)(tot[0] & 0xFFFF), n1 = (int32_t)(tot[1] & 0xFFFF);
+    const bool small = !g1 && max(n0, n1) <= kSmallTail && !step.st.prow && !(K1S_SKIP & 2);
+    const bool srows = step.st.rows && !(K1S_SKIP & 16);
+    int64_t tpre[2] = {0, 0};
+    if (small && srows && threadIdx.x < (t1 ? 64 : 128)) {
+        if (t1) small_tail_bounds<true>(step.st, tpre);
+        else small_tail_bounds<false>(step.st, tpre);
+    }
+#endif
     for (int32_t c0 = 0; c0 < ((K1S_SKIP & 1) ? 0 : nst); c0 += kSRec) {  // (workgroup-uniform)
         const int32_t m = min(kSRec, nst - c0);
         if (c0 > 0) {  // this chunk's records from HBM (L2: written by this workgroup)
@@ -495,6 +574,14 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
     CRANE_TSTAMP(a.trace, wg, 5);
     // ---- D: the fused pass's tail
     if (K1S_SKIP & 2) return;
+#if K1S_RTAIL
+    if (small) {  // (workgroup-uniform) wave T takes kind T, or wave 0 both; the other waves leave
+        if (threadIdx.x >= (t1 ? 64 : 128)) return;
+        if (t1) small_tail<true>(s1l, n0, n1, ssh, step, blk, tpre, srows, a.trace, wg);
+        else small_tail<false>(s1l, n0, n1, ssh, step, blk, tpre, srows, a.trace, wg);
+        return;
+    }
+#endif
     if (t1) {
         if (threadIdx.x >= 64) return;
         if (threadIdx.x < 2) {  // the block's flat maxima into wave 0's slot (tile rows read it)

@@ -859,4 +859,73 @@ __device__ __forceinline__ void step_tile_rows(const Step1* s1l, const Step1* sr
     }
 }
 
+// ---- step_sort_publish + step_tile_rows for a block of few one-step records, in registers.
+// At 3 % stepped nodes a 256-node block holds about ten records per kind: the sorted LDS copy, the
+// scans and the searches above are then three barriers and five LDS round trips for a few hundred
+// bytes.  None of it is needed, not even the sort.  With a kind's n <= 32 records one per lane,
+//   a record's sorted position is #{records before it} (before: smaller bp, ties by slot), its
+//   pm1 the max of k1 over those and itself, its sm0 the max of k0 over the others;
+//   a tile bound v has count_le = #{bp <= v}, pmL[c - 1] = max{k1 : bp <= v} (the bound lo) and
+//   smL[c] = max{k0 : bp > v} (hi)
+// — one question asked of every record j, broadcast from lane j (readlane: no LDS, no scan, no
+// search): is it under this lane's threshold w (bp < w, or bp == w and j < tl)?  Lanes 0-31 ask
+// it as record `lane` (w its bp, tl its slot), lanes 32-63 as tile item lane - 32 of a round of 32
+// (tile x >> 1, bound x & 1; w the bound, tl past every slot), in the same loop: small_scan.
+// Wave-local, no barrier.  The words written are step_sort_publish's and step_tile_rows' without
+// st.prow, bit for bit (keys are >= -1).
+struct SmallScan {
+    int32_t cnt;  // records under the threshold
+    int32_t a;    // max k1 over them
+    int32_t b;    // max k0 over the others
+};
+// r: lane j < n holds record j of the kind (n wave-uniform)
+__device__ __forceinline__ SmallScan small_scan(const Step1& r, int n, int64_t w, int tl) {
+    SmallScan s{0, -1, -1};
+    for (int j = 0; j < n; ++j) {
+        const int64_t bj = readlane64(r.bp, j);
+        const int32_t k0j = __builtin_amdgcn_readlane(r.k0, j), k1j = __builtin_amdgcn_readlane(r.k1, j);
+        const bool under = bj < w || (bj == w && j < tl);
+        s.cnt += under;
+        s.a = max(s.a, under ? k1j : -1);
+        s.b = max(s.b, under ? -1 : k0j);
+    }
+    return s;
+}
+// the bound of item lane `lane` (32-63) of the round whose first tile is t0, for kind T; other lanes 0
+__device__ __forceinline__ int64_t small_tile_bound(const StepTables& st, int T, int t0, int lane) {
+    const int t = t0 + ((lane - 32) >> 1);
+    return lane >= 32 && t < st.ntiles ? st.tiles[kTileStat * t + 2 * T + (lane & 1)] : 0;
+}
+// the records' part of a scan with w = the lane's own bp, tl = lane: step_sort_publish's stores
+__device__ __forceinline__ void small_records_store(int T, int n, const Step1& r, const SmallScan& s,
+                                                    const StepTables& st, int64_t blk) {
+    const int lane = threadIdx.x & 63;
+    if (lane < n) {
+        const int64_t at = s1_at(st, T, blk) + s.cnt;
+        st.single[at] = r;
+        st.pm1[at] = max(s.a, r.k1);  // sorted positions <= its own
+        st.sm0[at] = s.b;             // ... >= its own (itself is not under its threshold)
+    }
+}
+// the items' part of a scan with w = small_tile_bound, tl = 64: the bounds of a tile (adjacent
+// lanes) combine as step_tile_rows' do, and the kind stores its own two words of the tile's row
+// (kind 0 .x / .z, kind 1 .y / .w: two waves taking a kind each exchange nothing).  fl: the
+// block's flat maximum of the kind.  Every lane of the wave calls it (DPP).
+__device__ __forceinline__ void small_row_store(int T, int t0, const SmallScan& s, int32_t fl, const StepTables& st,
+                                                int64_t blk) {
+    const int lane = threadIdx.x & 63, t = t0 + ((lane - 32) >> 1);
+    const bool hi_b = lane & 1;
+    // lo: records stepped by it, their keys after; hi: records stepping after it, before
+    const int32_t c = s.cnt, u = hi_b ? s.b : s.a;
+    const int32_t co = quad_xor1(c), uo = quad_xor1(u);
+    const int32_t jl = hi_b ? co : c, jh = hi_b ? c : co;
+    // a kind without pods here (lo = INT64_MAX, hi = INT64_MIN) gives jl = n > jh = 0
+    const int32_t um = jl > jh ? -1 : max(fl, max(u, uo)), jp = jl > jh ? 0 : (jl | (jh << 16));
+    if (lane >= 32 && !hi_b && t < st.ntiles) {
+        int32_t* row = reinterpret_cast<int32_t*>(st.rows + ((int64_t)t * st.nblk + blk));
+        row[T] = um;
+        row[2 + T] = jp;
+    }
+}
+
 }  // namespace crane
