@@ -43,25 +43,6 @@ namespace crane {
 // walking its expiries in order with the record read from LDS term by term, spent 4.9 us per
 // workgroup here: a chain of dependent LDS reads; a lane per (node, kind, candidate) doubled the
 // emitting waves for 1 % more time).  The outputs are step_emit_one's, bit for bit.
-__device__ __forceinline__ int64_t readfirstlane64(int64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// score_at for a record in LDS with its terms read one at a time (a rolled loop: two fields in
-// registers at a time — the emit's keys are computed side by side, so each one's own latency
-// matters less than the registers a copy of the record would hold)
-template <int PD, int PR>
-__device__ __forceinline__ int32_t score_at_lds(int64_t t, const NodeRec<PD, PR>& r, double wsum, int32_t noprio,
-                                                double winv) {
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < PR; ++k)
-        if (t < r.e_prio[k]) s += r.t[k];  // stats.go:124-133, policy order
-    return score_of_sum(s, t < r.e_hv ? r.pen : 0, wsum, noprio, winv);
-}
-
 // K1S_SKIP (cost ablation builds only, tools/gpu_k1_ablate.sh; wrong tables): 1 no emit tasks,
 // 2 no tail (sort / pieces / tile rows), 4 no record staging, 8 middle pieces left raw (no
 // elementary pieces: the tables stay right, K3s reads every piece), 16 no tile rows
@@ -79,12 +60,6 @@ __device__ __forceinline__ int32_t score_at_lds(int64_t t, const NodeRec<PD, PR>
 #endif
 #ifndef K1S_FULL  // the instance for a policy of exactly 4 predicates / 6 priorities / 2 windows (A/B: 0 off)
 #define K1S_FULL 1
-#endif
-#ifndef K1S_EMIT_SCORE  // the emit's score from the candidates in registers, terms loaded together (A/B: 0 off)
-#define K1S_EMIT_SCORE 1
-#endif
-#ifndef K1S_PUB1  // step_publish folded into the slots' exchange (one barrier; A/B: 0 its own barrier)
-#define K1S_PUB1 1
 #endif
 #ifndef K1S_SREC
 #define K1S_SREC 64
@@ -144,7 +119,6 @@ __device__ __forceinline__ void emit_task(const NodeRec<PD, PR>& r, int64_t n, i
     const int rk1 = rk0 - (fb ? 1 : 0);
     // one score per instant serves both kinds (the Filter only gates kind 0's key): score_at with
     // the expiries already in c[] and the terms read side by side (one LDS wait, not one per term)
-#if K1S_EMIT_SCORE
     double tk[PR];
 #pragma unroll
     for (int k = 0; k < PR; ++k) tk[k] = r.t[k];
@@ -152,9 +126,6 @@ __device__ __forceinline__ void emit_task(const NodeRec<PD, PR>& r, int64_t n, i
 #pragma unroll
     for (int k = 0; k < PR; ++k) ssum = cq < c[k] ? ssum + tk[k] : ssum;  // stats.go:124-133, policy order
     const int64_t pk = pack_key(score_of_sum(ssum, cq < c[PR] ? r.pen : 0, wsum, noprio, winv), n);
-#else
-    const int64_t pk = pack_key(score_at_lds<PD, PR>(cq, r, wsum, noprio, winv), n);
-#endif
     // the score at tmin: phase A's, kept in the record's slot words (dw[5])
     const int64_t pk0 = pack_key(dw[5], n);
 #pragma unroll
@@ -206,18 +177,16 @@ __device__ __forceinline__ void emit_task(const NodeRec<PD, PR>& r, int64_t n, i
 template <int BS, class Rec>
 __device__ __forceinline__ void tail(bool g1, Rec* lrec, Step1* s1l, Step1* srt, StepShared& ssh, const K1Step& step,
                                      int64_t blk, unsigned long long* trace, int64_t wg) {
-    if (g1) step_sort_publish_global<BS>(ssh, step.st, blk);
-    else step_sort_publish<BS, kSCap>(s1l, srt, ssh, step.st, blk);
-    CRANE_TSTAMP(trace, wg, 6);
-    if (step.st.rows && !(K1S_SKIP & 16)) {
-        int64_t tpre = 0;  // this thread's first tile-row bound (step_tile_rows)
-        tile_prefetch(step.st, &tpre);
-        constexpr int kPc = ((int)(kSRec * sizeof(Rec)) / PieceScr::bytes_per_piece) & ~3;
-        const PieceScr ps{reinterpret_cast<unsigned char*>(lrec), (K1S_SKIP & 8) ? 0 : (kPc < 128 ? kPc : 128)};
-        step_pieces<BS>(ssh, step.st, blk, ps);
-        if (g1) step_tile_rows<BS, kSCap, true>(s1l, srt, ssh, step.st, blk, &tpre, ps);
-        else step_tile_rows<BS, kSCap, false>(s1l, srt, ssh, step.st, blk, &tpre, ps);
-    }
+    constexpr int kPc = ((int)(kSRec * sizeof(Rec)) / PieceScr::bytes_per_piece) & ~3;
+    const PieceScr ps{reinterpret_cast<unsigned char*>(lrec), (K1S_SKIP & 8) ? 0 : (kPc < 128 ? kPc : 128)};
+#if K1S_SKIP & 16
+    StepTables st = step.st;
+    st.rows = nullptr;
+#else
+    const StepTables& st = step.st;
+#endif
+    // (no early tile_prefetch: the first tile bounds load behind the sort)
+    step_epilogue<BS, kSCap>(g1, s1l, srt, ssh, st, blk, nullptr, ps, trace, wg);
     CRANE_TSTAMP(trace, wg, 4);
 }
 
@@ -254,7 +223,7 @@ __device__ __forceinline__ void small_tail(const Step1* s1l, int32_t n0, int32_t
     for (int k = 0; k < NK; ++k) {
         const int T = T0 + k;
         n[k] = __builtin_amdgcn_readfirstlane(T ? n1 : n0);
-        fl[k] = max(max(ssh.fm[T][0], ssh.fm[T][1]), max(ssh.fm[T][2], ssh.fm[T][3]));
+        fl[k] = block_flat_max<256>(ssh, T);
         r[k].bp = 0;
         r[k].k0 = r[k].k1 = -1;
         if (lane < n[k]) r[k] = s1l[T * kSCap + lane];
@@ -347,7 +316,7 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
     double hvl = 0.0;
     int64_t hvt = kTsInvalid;
     if (a.buckets) {
-        // (+ the delta form's anchor counts: kernels.hip)
+        // (+ the delta form's anchor counts: node_rec.hpp bucket_anchor_counts)
         const uint32_t* __restrict__ base = a.bucket_base ? a.bucket_base : a.buckets;
         uint32_t bz[kMaxWin];
 #pragma unroll
@@ -355,10 +324,7 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
             bc[b] = b < nwin ? (a.buckets + first)[(int64_t)b * N + lo] : 0u;
             bz[b] = b < nwin ? (base + first)[(int64_t)b * N + lo] : 0u;
         }
-        if (a.bucket_base) {  // (rows past n_win read as 0)
-#pragma unroll
-            for (int b = 0; b < kMaxWin; ++b) bc[b] = bz[b] + bc[b] - (b + 1 < kMaxWin ? bc[b + 1] : 0u);
-        }
+        if (a.bucket_base) bucket_anchor_counts(bz, bc);  // (rows past n_win read as 0)
     } else if (a.hv) {
         hvl = a.hv[first + lo];
         hvt = a.hv_ts ? a.hv_ts[first + lo] : a.hv_ts_counts;
@@ -401,14 +367,7 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
     // priorities in policy order: score_at(tmin)'s ordered sum and the in-range expiries both
     // pod kinds share (priorities, hot value); e_fail is kind 0's too (DaemonSet pods bypass)
     double s = 0.0;
-    int cnt1 = 0;
-    int64_t mn1 = INT64_MAX, mx1 = INT64_MIN;
-    auto add = [&](int64_t e, int& c, int64_t& mn, int64_t& mx) {
-        const bool in = e > tmin && e <= tmax;
-        c += in;
-        mn = in ? min(mn, e) : mn;
-        mx = in ? max(mx, e) : mx;
-    };
+    StepRange both;
     // the terms stay in registers (they replace the rows' ts / usage) until a stepped lane has
     // its record slot (after B): no second read of the rows
     int64_t ep[PR];
@@ -422,33 +381,24 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
         ep[k] = use ? e : kTsInvalid;
         tp[k] = use ? term : 0.0;
         s = tmin < ep[k] ? s + tp[k] : s;  // stats.go:124-133
-        add(ep[k], cnt1, mn1, mx1);
+        both.add(ep[k], tmin, tmax);
     }
-    add(hr.e_hv, cnt1, mn1, mx1);
-    int cnt0 = cnt1;
-    int64_t mn0 = mn1, mx0 = mx1;
-    add(e_fail, cnt0, mn0, mx0);
-    if (!valid) cnt0 = cnt1 = 0;
+    both.add(hr.e_hv, tmin, tmax);
     const int32_t s0 = score_of_sum(s, tmin < hr.e_hv ? hr.pen : 0, step.wsum, step.noprio, step.winv);
-    const bool multi0 = cnt0 > 0 && mn0 != mx0, multi1 = cnt1 > 0 && mn1 != mx1;
+    StepRange g[2];
     StepSlots so;
-    so.flat0 = valid && cnt0 == 0 && !(tmin < e_fail) ? pack_key(s0, n) : -1;
-    so.flat1 = valid && cnt1 == 0 ? pack_key(s0, n) : -1;
+    step_classify(both, e_fail, valid, s0, n, tmin, tmax, g, so);
     CRANE_TSTAMP(a.trace, wg, 2);
     // ---- B: slots (wave prefix sums, the waves' totals exchanged once: one barrier)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint32_t w0 = (cnt0 ? (multi0 ? 2u : 1u) : 0u) | (multi0 ? (uint32_t)(cnt0 - 1) << 16 : 0u);
-    const uint32_t w1 = (cnt1 ? (multi1 ? 2u : 1u) : 0u) | (multi1 ? (uint32_t)(cnt1 - 1) << 16 : 0u);
-    const uint32_t w2 = (cnt0 | cnt1) ? 1u : 0u;
+    const uint32_t w0 = g[0].word(), w1 = g[1].word(), w2 = (g[0].cnt | g[1].cnt) ? 1u : 0u;
     uint32_t e0 = wave_scan_add(w0), e1 = wave_scan_add(w1), e2 = wave_scan_add(w2);
-#if K1S_PUB1
     // the flat maxima per wave go out with the totals (step_publish's exchange: one barrier for both)
     const int32_t fm0 = wave_max(so.flat0), fm1 = wave_max(so.flat1);
     if (lane == 0) {
         ssh.fm[0][wv] = fm0;
         ssh.fm[1][wv] = fm1;
     }
-#endif
     if (lane == 63) {
         xch[0][wv] = e0;
         xch[1][wv] = e1;
@@ -465,10 +415,7 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
         base[k] = (wv > 0 ? x.x : 0u) + (wv > 1 ? x.y : 0u) + (wv > 2 ? x.z : 0u);
         tot[k] = x.x + x.y + x.z + x.w;
     }
-    const int32_t slot0 = cnt0 ? (int32_t)((base[0] + e0) & 0xFFFF) : -1;
-    const int32_t mslot0 = multi0 ? (int32_t)((base[0] + e0) >> 16) : 0;
-    const int32_t slot1 = cnt1 ? (int32_t)((base[1] + e1) & 0xFFFF) : -1;
-    const int32_t mslot1 = multi1 ? (int32_t)((base[1] + e1) >> 16) : 0;
+    step_slots(g, base[0] + e0, base[1] + e1, so);
     const int32_t rs = (int32_t)(base[2] + e2);  // rank among the block's stepped nodes
     const int32_t nst = (int32_t)tot[2];
     if (threadIdx.x == 0) {
@@ -477,30 +424,20 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
         ssh.lc[1][0] = (int32_t)(tot[1] & 0xFFFF);
         ssh.lc[1][1] = (int32_t)(tot[1] >> 16);
     }
-#if K1S_PUB1
     // step_publish's stores from the exchanged values (ssh.lc is read after the next barrier)
-    if (threadIdx.x < 2) {
-        const int T = threadIdx.x;
-        step.st.flat[blk * 2 + T] = max(max(ssh.fm[T][0], ssh.fm[T][1]), max(ssh.fm[T][2], ssh.fm[T][3]));
-    } else if (threadIdx.x < 6) {
-        const int L = threadIdx.x - 2;  // kind L >> 1: one-step records (L & 1 = 0) / middle pieces
-        step.st.cnt[blk * 4 + L] = (int32_t)((L & 1) ? tot[L >> 1] >> 16 : tot[L >> 1] & 0xFFFF);
-    }
+    step_publish_store<BS>(ssh, step.st, blk, [&](int L) {
+        return (int32_t)((L & 1) ? tot[L >> 1] >> 16 : tot[L >> 1] & 0xFFFF);
+    });
+    // one-step records staged in LDS, or (more of a kind than it holds) in st.stage
     const bool g1 = (int32_t)max(tot[0] & 0xFFFF, tot[1] & 0xFFFF) > min(kSCap, step.st.lds_cap);
     CRANE_TSTAMP(a.trace, wg, 3);
-#else
-    step_publish<BS>(so, ssh, step.st, blk);  // flat maxima, counts (its barrier: ssh.lc final)
-    CRANE_TSTAMP(a.trace, wg, 3);
-    // one-step records staged in LDS, or (more of a kind than it holds) in st.stage
-    const bool g1 = max(ssh.lc[0][0], ssh.lc[1][0]) > min(kSCap, step.st.lds_cap);
-#endif
     const S1Out s1o{s1l, step.st.stage + blk * 2 * step.st.bs, g1, (int64_t)kSCap, step.st.s1pad};
     // ---- C: the stepped nodes' records in LDS, chunk by chunk, and their (node, kind) items.
     // The first kSRec stepped nodes write their part (e_fail, pen, e_hv, slots) into the LDS
     // records now; any further ones into their node's record slot in HBM (step.srec, the node
     // records the keys-only step leaves stale anyway: the slots go in e_pred, which the emit does
     // not read), fetched chunk by chunk — no per-lane state lives across the chunks.
-    const bool stepped = (cnt0 | cnt1) != 0;
+    const bool stepped = (g[0].cnt | g[1].cnt) != 0;
     auto put = [&](Rec* r) {  // (called with an LDS and a global pointer: no flat stores)
         r->e_fail = e_fail;
         r->pen = hr.pen;
@@ -511,11 +448,11 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
             r->t[k] = tp[k];
         }
         int32_t* dw = reinterpret_cast<int32_t*>(r->e_pred);
-        dw[0] = slot0;
-        dw[1] = mslot0;
-        dw[2] = slot1;
-        dw[3] = mslot1;
-        dw[4] = (multi0 ? 1 : 0) | (multi1 ? 2 : 0);
+        dw[0] = so.slot0;
+        dw[1] = so.mslot0;
+        dw[2] = so.slot1;
+        dw[3] = so.mslot1;
+        dw[4] = (so.multi0 ? 1 : 0) | (so.multi1 ? 2 : 0);
         dw[5] = s0;  // score_at(tmin): the keys before a node's first step
     };
     if (stepped && !(K1S_SKIP & 4)) {
@@ -586,7 +523,7 @@ __device__ __forceinline__ void k1_stream_body(const K1Args& a, const K1Step& st
         if (threadIdx.x >= 64) return;
         if (threadIdx.x < 2) {  // the block's flat maxima into wave 0's slot (tile rows read it)
             const int T = threadIdx.x;
-            ssh.fm[T][0] = max(max(ssh.fm[T][0], ssh.fm[T][1]), max(ssh.fm[T][2], ssh.fm[T][3]));
+            ssh.fm[T][0] = block_flat_max<BS>(ssh, T);
         }
         tail<64>(g1, lrec, s1l, srt, ssh, step, blk, a.trace, wg);
         return;

@@ -213,10 +213,7 @@ void k1_node_pass(K1Args a, K1Step step) {
             bc[b] = b < pol.n_win ? (buckets + first)[(int64_t)b * N + lo] : 0u;
             bz[b] = b < pol.n_win ? (base + first)[(int64_t)b * N + lo] : 0u;
         }
-        if (a.bucket_base) {  // (rows past n_win read as 0)
-#pragma unroll
-            for (int b = 0; b < kMaxWin; ++b) bc[b] = bz[b] + bc[b] - (b + 1 < kMaxWin ? bc[b + 1] : 0u);
-        }
+        if (a.bucket_base) bucket_anchor_counts(bz, bc);  // (rows past n_win read as 0)
     }
     if (!buckets && !hx && hv) {
         hvl = hv[first + lo];
@@ -320,20 +317,13 @@ void k1_node_pass(K1Args a, K1Step step) {
         }
         __syncthreads();
         CRANE_TSTAMP(a.trace, blockIdx.x, 5);
-        if (g1) step_sort_publish_global<kK1Threads>(ssh, step.st, blk);
-        else step_sort_publish<kK1Threads, CAP>(s1l, s1s, ssh, step.st, blk);
-        CRANE_TSTAMP(a.trace, blockIdx.x, 6);
-        if (step.st.rows) {
-            // keys-only: the middle pieces' scratch is the staged records' LDS past the sorted
-            // one-step copy (dead after the emit); with the records kept there is none
-            constexpr int kS1 = 2 * (int)sizeof(Step1) * CAP;
-            constexpr int kDyn = (int)sizeof(Rec) * (kK1Threads < kK1RecCap ? kK1Threads : kK1RecCap);
-            constexpr int kPc = kDyn > kS1 ? ((kDyn - kS1) / PieceScr::bytes_per_piece) & ~3 : 0;
-            const PieceScr ps{smem + kS1, out ? 0 : (kPc < 128 ? kPc : 128)};
-            step_pieces<kK1Threads>(ssh, step.st, blk, ps);
-            if (g1) step_tile_rows<kK1Threads, CAP, true>(s1l, s1s, ssh, step.st, blk, &tpre, ps);
-            else step_tile_rows<kK1Threads, CAP, false>(s1l, s1s, ssh, step.st, blk, &tpre, ps);
-        }
+        // keys-only: the middle pieces' scratch is the staged records' LDS past the sorted
+        // one-step copy (dead after the emit); with the records kept there is none
+        constexpr int kS1 = 2 * (int)sizeof(Step1) * CAP;
+        constexpr int kDyn = (int)sizeof(Rec) * (kK1Threads < kK1RecCap ? kK1Threads : kK1RecCap);
+        constexpr int kPc = kDyn > kS1 ? ((kDyn - kS1) / PieceScr::bytes_per_piece) & ~3 : 0;
+        const PieceScr ps{smem + kS1, out ? 0 : (kPc < 128 ? kPc : 128)};
+        step_epilogue<kK1Threads, CAP>(g1, s1l, s1s, ssh, step.st, blk, &tpre, ps, a.trace, blockIdx.x);
     } else {
         __syncthreads();
     }

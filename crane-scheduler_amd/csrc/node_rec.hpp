@@ -27,6 +27,13 @@ __device__ __forceinline__ int64_t sat_add(int64_t a, int64_t b) {
     return o ? (b > 0 ? INT64_MAX : INT64_MIN) : r;  // (selects: no branch around a caller's loads)
 }
 
+// The delta form of K2 keeps its anchor's counts (bz) beside its adjustments (bc, the buckets K1
+// reads): the node's window-rank counts from both, in place (rows past n_win read as 0).
+__device__ __forceinline__ void bucket_anchor_counts(const uint32_t (&bz)[kMaxWin], uint32_t (&bc)[kMaxWin]) {
+#pragma unroll
+    for (int b = 0; b < kMaxWin; ++b) bc[b] = bz[b] + bc[b] - (b + 1 < kMaxWin ? bc[b + 1] : 0u);
+}
+
 // Predicate and priority parts of the record from the metric rows the policy reads
 // (pt / pv: predicate k's (ts, value); qt / qv: priority k's), then e_fail.
 template <int PD, int PR>

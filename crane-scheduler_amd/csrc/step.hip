@@ -79,16 +79,10 @@ __global__ __launch_bounds__(kStepSeg) void k3a_steps(const NodeRec<PD, PR>* __r
     step_publish<kStepSeg>(o, sh, st, blockIdx.x);
     if (n < N && (o.slot0 >= 0 || o.slot1 >= 0)) step_emit<PD, PR>(r, n, tmin, tmax, wsum, noprio, o, st, blockIdx.x, S1Out{s1l, nullptr, false, 2 * kStepSeg, 0});
     __syncthreads();
-    step_sort_publish<kStepSeg>(s1l, s1s, sh, st, blockIdx.x);
-    if (st.rows) {
-        int64_t pre;
-        tile_prefetch(st, &pre);
-        // middle pieces' scratch: s1l past the prefix / suffix maxima ([2][2 * kStepSeg] int32 each)
-        const PieceScr ps{reinterpret_cast<unsigned char*>(s1l) + 32 * kStepSeg,
-                          ((int)sizeof(s1l) - 32 * kStepSeg) / PieceScr::bytes_per_piece & ~3};
-        step_pieces<kStepSeg>(sh, st, blockIdx.x, ps);
-        step_tile_rows<kStepSeg>(s1l, s1s, sh, st, blockIdx.x, &pre, ps);
-    }
+    // middle pieces' scratch: s1l past the prefix / suffix maxima ([2][2 * kStepSeg] int32 each)
+    const PieceScr ps{reinterpret_cast<unsigned char*>(s1l) + 32 * kStepSeg,
+                      ((int)sizeof(s1l) - 32 * kStepSeg) / PieceScr::bytes_per_piece & ~3};
+    step_epilogue<kStepSeg, 2 * kStepSeg>(false, s1l, s1s, sh, st, blockIdx.x, nullptr, ps, nullptr, blockIdx.x);
 }
 
 // ---------------------------------------------------------------- K3s
@@ -298,13 +292,8 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
     const int64_t tsv = ts[lane < kTileStat ? lane : 0];
     for (int i = threadIdx.x; i < 2 * kK3sPods; i += TH) tree[i] = -1;
     if (threadIdx.x < 2) umax[threadIdx.x] = -1;
-    auto stat = [&](int k) {
-        const uint32_t lo32 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)tsv, k);
-        const uint32_t hi32 = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)tsv >> 32), k);
-        return (int64_t)(((uint64_t)hi32 << 32) | lo32);
-    };
-    const int64_t tlo[2] = {stat(0), stat(2)}, thi[2] = {stat(1), stat(3)};
-    const int32_t cn = (int32_t)stat(4), cd = (int32_t)stat(5);
+    const int64_t tlo[2] = {readlane64(tsv, 0), readlane64(tsv, 2)}, thi[2] = {readlane64(tsv, 1), readlane64(tsv, 3)};
+    const int32_t cn = (int32_t)readlane64(tsv, 4), cd = (int32_t)readlane64(tsv, 5);
     const int32_t klo[2] = {0, cn}, khi[2] = {cn, cn + cd};
     const bool any[2] = {cn > 0, cd > 0};
 #if K3S_BUCKETS

@@ -145,45 +145,6 @@ __device__ __forceinline__ void batch_range_reduce(int64_t mn, int64_t mx, int64
         tmax = max(tmax, smx[i]);
     }
 }
-// Per-wave form (no LDS, no barrier): every wave reads all tile stats itself — lane l
-// the tiles l, l + 64, ... — in two parts: batch_range_wave_load keeps the first two
-// tiles' bounds in registers (issued early), batch_range_wave_reduce folds them, reads
-// any further tiles and reduces over the wave.
-struct TileBounds {
-    int64_t mn[2], mx[2];
-};
-__device__ __forceinline__ void batch_range_wave_load(const int64_t* __restrict__ tile_mm, int32_t ntiles,
-                                                      TileBounds& tb) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int i = lane + 64 * h;
-        tb.mn[h] = INT64_MAX;
-        tb.mx[h] = INT64_MIN;
-        if (i < ntiles) {
-            const int64_t* ts = tile_mm + kTileStat * i;
-            tb.mn[h] = min(ts[0], ts[2]);
-            tb.mx[h] = max(ts[1], ts[3]);
-        }
-    }
-}
-__device__ __forceinline__ void batch_range_wave_reduce(const int64_t* __restrict__ tile_mm, int32_t ntiles,
-                                                        const TileBounds& tb, int64_t& tmin, int64_t& tmax) {
-    int64_t mn = min(tb.mn[0], tb.mn[1]), mx = max(tb.mx[0], tb.mx[1]);
-    for (int i = (threadIdx.x & 63) + 128; i < ntiles; i += 64) {
-        const int64_t* ts = tile_mm + kTileStat * i;
-        mn = min(mn, min(ts[0], ts[2]));
-        mx = max(mx, max(ts[1], ts[3]));
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        mn = min(mn, (int64_t)__shfl_xor((long long)mn, o));
-        mx = max(mx, (int64_t)__shfl_xor((long long)mx, o));
-    }
-    tmin = mn;
-    tmax = mx;
-}
-
 template <int BS>
 __device__ __forceinline__ void batch_range(const int64_t* __restrict__ tile_mm, int32_t ntiles, int64_t* smn,
                                             int64_t* smx, int64_t& tmin, int64_t& tmax) {
@@ -223,9 +184,15 @@ __device__ __forceinline__ uint32_t wg_excl_scan_u32(uint32_t v, uint32_t* part)
     return pre + x - v;
 }
 
+// a 64-bit value of lane j / of the first active lane, uniform
 __device__ __forceinline__ int64_t readlane64(int64_t v, int j) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), j);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ int64_t readfirstlane64(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
@@ -246,7 +213,6 @@ struct StepSlots {
     int32_t flat0 = -1, flat1 = -1;
     int32_t slot0 = -1, slot1 = -1;    // >= 0: stepped (first one-step record slot)
     int32_t mslot0 = 0, mslot1 = 0;    // first middle-piece slot
-    int8_t nb0 = 0, nb1 = 0;           // in-range expiries (with repeats): one-step record iff 1 distinct
     bool multi0 = false, multi1 = false;
 };
 
@@ -256,42 +222,83 @@ struct StepShared {
     int32_t fm[2][16];  // per-wave flat maxima (<= 1024 threads)
     int32_t pn[2];      // per kind: elementary pieces after step_pieces, -1 = raw pieces
 };
+// the block's flat maximum of kind T from the per-wave maxima (after the barrier behind their stores)
+template <int BS>
+__device__ __forceinline__ int32_t block_flat_max(const StepShared& sh, int T) {
+    int32_t m = sh.fm[T][0];
+#pragma unroll
+    for (int i = 1; i < BS / 64; ++i) m = max(m, sh.fm[T][i]);
+    return m;
+}
 
-// Phase 1.  A node with one distinct in-range expiry (a predicate's expiry
-// equals its metric's priority expiry when both use one metric) is one record;
-// otherwise two half-line records and cnt - 1 middle-piece slots are reserved
-// (repeated expiries give empty pieces, harmless: they cover no time).
+// The classifier every producer shares.  StepRange: a node's expiries inside the batch range
+// (tmin, tmax] for one pod kind — the only ones that can change its key over the batch — folded
+// one at a time: their number (with repeats), minimum and maximum.  A node with one distinct
+// in-range expiry (a predicate's expiry equals its metric's priority expiry when both use one
+// metric) is one record; otherwise two half-line records and cnt - 1 middle-piece slots are
+// reserved (repeated expiries give empty pieces, harmless: they cover no time).
+struct StepRange {
+    int cnt = 0;
+    int64_t mn = INT64_MAX, mx = INT64_MIN;
+    __device__ __forceinline__ void add(int64_t e, int64_t tmin, int64_t tmax) {
+        const bool in = e > tmin && e <= tmax;
+        cnt += in;
+        mn = in ? min(mn, e) : mn;
+        mx = in ? max(mx, e) : mx;
+    }
+    __device__ __forceinline__ bool multi() const { return cnt > 0 && mn != mx; }  // (cnt == 0: mn > mx)
+    // what the node takes of its kind's spans: one-step records | middle pieces << 16
+    __device__ __forceinline__ uint32_t word() const {
+        return (cnt ? (multi() ? 2u : 1u) : 0u) | (multi() ? (uint32_t)(cnt - 1) << 16 : 0u);
+    }
+};
+// Both kinds' ranges g[T] from the expiries they share (both: the priorities', the hot value's):
+// kind 0 also steps at e_fail (DaemonSet pods, kind 1, bypass the Filter); a lane without a node
+// (!valid) has none.  Sets o's flat keys — the node's key at tmin (score s0) when nothing steps,
+// else -1 — and multi flags.
+__device__ __forceinline__ void step_classify(const StepRange& both, int64_t e_fail, bool valid, int32_t s0, int64_t n,
+                                              int64_t tmin, int64_t tmax, StepRange (&g)[2], StepSlots& o) {
+    g[0] = g[1] = both;
+    g[0].add(e_fail, tmin, tmax);
+    if (!valid) g[0].cnt = g[1].cnt = 0;
+    o.multi0 = g[0].multi();
+    o.multi1 = g[1].multi();
+    o.flat0 = valid && g[0].cnt == 0 && !(tmin < e_fail) ? pack_key(s0, n) : -1;  // key_of at tmin
+    o.flat1 = valid && g[1].cnt == 0 ? pack_key(s0, n) : -1;
+}
+// The node's slots from at[T]: its kind's span base + the exclusive prefix of the word()s before it
+// (packed like word(): the sums stay under 2^16).
+__device__ __forceinline__ void step_slots(const StepRange (&g)[2], uint32_t at0, uint32_t at1, StepSlots& o) {
+    o.slot0 = g[0].cnt ? (int32_t)(at0 & 0xFFFF) : -1;
+    o.mslot0 = g[0].multi() ? (int32_t)(at0 >> 16) : 0;
+    o.slot1 = g[1].cnt ? (int32_t)(at1 & 0xFFFF) : -1;
+    o.mslot1 = g[1].multi() ? (int32_t)(at1 >> 16) : 0;
+}
+// the expiries both kinds share, of a record
+template <int PD, int PR>
+__device__ __forceinline__ StepRange step_range(const NodeRec<PD, PR>& r, int64_t tmin, int64_t tmax) {
+    StepRange sh;
+#pragma unroll
+    for (int k = 0; k < PR; ++k) sh.add(r.e_prio[k], tmin, tmax);
+    sh.add(r.e_hv, tmin, tmax);
+    return sh;
+}
+
+// Phase 1 (the stand-alone K3a, threads with a node): spans taken with one LDS atomic per counter.
 template <int PD, int PR>
 __device__ __forceinline__ void step_count(const NodeRec<PD, PR>& r, int64_t n, int64_t tmin, int64_t tmax,
                                            double wsum, int32_t noprio, StepShared& sh, StepSlots& o) {
-    const int32_t s0 = score_at<PD, PR>(tmin, r, wsum, noprio);
-    // the in-range expiries both kinds share (priorities, hot value), then e_fail for kind 0
-    int cnt1 = 0;
-    int64_t mn1 = INT64_MAX, mx1 = INT64_MIN;
-    auto add = [&](int64_t e, int& c, int64_t& mn, int64_t& mx) {
-        const bool in = e > tmin && e <= tmax;
-        c += in;
-        mn = in ? min(mn, e) : mn;
-        mx = in ? max(mx, e) : mx;
-    };
+    StepRange g[2];
+    step_classify(step_range(r, tmin, tmax), r.e_fail, true, score_at<PD, PR>(tmin, r, wsum, noprio), n, tmin, tmax,
+                  g, o);
+    uint32_t at[2] = {0, 0};
 #pragma unroll
-    for (int k = 0; k < PR; ++k) add(r.e_prio[k], cnt1, mn1, mx1);
-    add(r.e_hv, cnt1, mn1, mx1);
-    int cnt0 = cnt1;
-    int64_t mn0 = mn1, mx0 = mx1;
-    add(r.e_fail, cnt0, mn0, mx0);  // DaemonSet pods bypass the Filter
-    auto kind = [&](auto Tc, int32_t& flat, int32_t& slot, int32_t& mslot, int8_t& nb, bool& multi) {
-        constexpr int T = decltype(Tc)::value;
-        const int cnt = T ? cnt1 : cnt0;
-        const int64_t mn = T ? mn1 : mn0, mx = T ? mx1 : mx0;
-        flat = cnt == 0 ? key_of<PD, PR>(T, tmin, s0, r, n) : -1;
-        multi = cnt > 0 && mn != mx;  // (cnt == 0: mn = INT64_MAX, mx = INT64_MIN)
-        nb = (int8_t)cnt;
-        slot = cnt == 0 ? -1 : atomicAdd(&sh.lc[T][0], multi ? 2 : 1);
-        mslot = multi ? atomicAdd(&sh.lc[T][1], cnt - 1) : 0;
-    };
-    kind(std::integral_constant<int, 0>{}, o.flat0, o.slot0, o.mslot0, o.nb0, o.multi0);
-    kind(std::integral_constant<int, 1>{}, o.flat1, o.slot1, o.mslot1, o.nb1, o.multi1);
+    for (int T = 0; T < 2; ++T) {
+        const uint32_t w = g[T].word();
+        if (w) at[T] = (uint32_t)atomicAdd(&sh.lc[T][0], (int32_t)(w & 0xFFFF));
+        if (w >> 16) at[T] |= (uint32_t)atomicAdd(&sh.lc[T][1], (int32_t)(w >> 16)) << 16;
+    }
+    step_slots(g, at[0], at[1], o);
 }
 
 // Phase 2, one (node, kind): the node's one-step records go to the workgroup's
@@ -396,61 +403,28 @@ __device__ __forceinline__ void step_emit(const NodeRec<PD, PR>& r, int64_t n, i
         step_emit_one<PD, PR>(r, n, 1, o.slot1, o.mslot1, o.multi1, tmin, tmax, wsum, noprio, st, blk, s1o, winv);
 }
 
-// Work item of the compacted emit: owner thread | kind << 12 | multi << 13 | slot << 14 | rs << 24,
-// and its first middle-piece slot in qm.
-// (rs: the node's record slot in the workgroup's LDS staging, < 256; slot < 1024)
-__device__ __forceinline__ void step_queue(const StepSlots& o, int32_t* nq, uint32_t* q, int32_t* qm, int rs) {
-    if (o.slot0 >= 0) {
-        const int i = atomicAdd(nq, 1);
-        q[i] = threadIdx.x | ((uint32_t)o.multi0 << 13) | ((uint32_t)o.slot0 << 14) | ((uint32_t)rs << 24);
-        qm[i] = o.mslot0;
-    }
-    if (o.slot1 >= 0) {
-        const int i = atomicAdd(nq, 1);
-        q[i] = threadIdx.x | (1u << 12) | ((uint32_t)o.multi1 << 13) | ((uint32_t)o.slot1 << 14) | ((uint32_t)rs << 24);
-        qm[i] = o.mslot1;
-    }
-}
-
-// K1's form of step_count + stepped-record staging + step_queue, called by every thread
-// of the workgroup (valid: the thread has a node): the per-lane counts are prefix-summed
+// K1's form of step_count + stepped-record staging + the emit's work queue, called by every
+// thread of the workgroup (valid: the thread has a node): the per-lane counts are prefix-summed
 // across the wave (DPP) and one lane takes the wave's spans with one LDS atomic per
 // counter, instead of a chain of per-lane returning atomics.  Slots are assigned in lane
 // order (any order is a valid one: K3s takes maxima).  keep: records written out (the
 // record slot is the thread's; every item queued), else the stepped records are staged in
 // lrec[0, CAP) and a node past the staging builds its own (self_emit; its queue items
 // are marked ~0u).
+// Work item q[i]: owner thread | kind << 12 | multi << 13 | slot << 14 | rs << 24, its first
+// middle-piece slot in qm[i] (rs: the node's record slot in the LDS staging, < 256; slot < 1024).
 template <int PD, int PR, int CAP>
 __device__ __forceinline__ void step_count_queue(const NodeRec<PD, PR>& r, bool valid, int64_t n, int64_t tmin,
                                                  int64_t tmax, double wsum, double winv, int32_t noprio,
                                                  bool keep, StepShared& sh, int32_t* nrec, int32_t* nq,
                                                  uint32_t* q, int32_t* qm, NodeRec<PD, PR>* lrec, StepSlots& o,
                                                  bool& self_emit) {
-    const int32_t s0 = score_at<PD, PR>(tmin, r, wsum, noprio, winv);
-    int cnt1 = 0;
-    int64_t mn1 = INT64_MAX, mx1 = INT64_MIN;
-    auto add = [&](int64_t e, int& c, int64_t& mn, int64_t& mx) {
-        const bool in = e > tmin && e <= tmax;
-        c += in;
-        mn = in ? min(mn, e) : mn;
-        mx = in ? max(mx, e) : mx;
-    };
-#pragma unroll
-    for (int k = 0; k < PR; ++k) add(r.e_prio[k], cnt1, mn1, mx1);
-    add(r.e_hv, cnt1, mn1, mx1);
-    int cnt0 = cnt1;
-    int64_t mn0 = mn1, mx0 = mx1;
-    add(r.e_fail, cnt0, mn0, mx0);  // DaemonSet pods bypass the Filter
-    if (!valid) cnt0 = cnt1 = 0;
-    o.multi0 = cnt0 > 0 && mn0 != mx0;
-    o.multi1 = cnt1 > 0 && mn1 != mx1;
-    o.nb0 = (int8_t)cnt0;
-    o.nb1 = (int8_t)cnt1;
-    o.flat0 = valid && cnt0 == 0 ? key_of<PD, PR>(0, tmin, s0, r, n) : -1;
-    o.flat1 = valid && cnt1 == 0 ? key_of<PD, PR>(1, tmin, s0, r, n) : -1;
+    StepRange g[2];
+    step_classify(step_range(r, tmin, tmax), r.e_fail, valid, score_at<PD, PR>(tmin, r, wsum, noprio, winv), n, tmin,
+                  tmax, g, o);
+    const int cnt0 = g[0].cnt, cnt1 = g[1].cnt;
     // per lane: one-step records | middle pieces << 16 per kind; stepped | queue items << 16
-    const uint32_t w0 = (cnt0 ? (o.multi0 ? 2u : 1u) : 0u) | (o.multi0 ? (uint32_t)(cnt0 - 1) << 16 : 0u);
-    const uint32_t w1 = (cnt1 ? (o.multi1 ? 2u : 1u) : 0u) | (o.multi1 ? (uint32_t)(cnt1 - 1) << 16 : 0u);
+    const uint32_t w0 = g[0].word(), w1 = g[1].word();
     const uint32_t w2 = ((cnt0 | cnt1) ? 1u : 0u) | (((cnt0 ? 1u : 0u) + (cnt1 ? 1u : 0u)) << 16);
     // exclusive prefixes and the wave's totals (lane 63's inclusive prefix)
     uint32_t e0 = wave_scan_add(w0);
@@ -479,10 +453,7 @@ __device__ __forceinline__ void step_count_queue(const NodeRec<PD, PR>& r, bool 
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) b[k] = __builtin_amdgcn_readlane(b[k], 63);
-    o.slot0 = cnt0 ? b[0] + (int32_t)(e0 & 0xFFFF) : -1;
-    o.mslot0 = o.multi0 ? b[1] + (int32_t)(e0 >> 16) : 0;
-    o.slot1 = cnt1 ? b[2] + (int32_t)(e1 & 0xFFFF) : -1;
-    o.mslot1 = o.multi1 ? b[3] + (int32_t)(e1 >> 16) : 0;
+    step_slots(g, ((uint32_t)b[0] | (uint32_t)b[1] << 16) + e0, ((uint32_t)b[2] | (uint32_t)b[3] << 16) + e1, o);
     self_emit = false;
     if (cnt0 | cnt1) {
         int rs = b[4] + (int32_t)(e2 & 0xFFFF);
@@ -507,6 +478,14 @@ __device__ __forceinline__ void step_count_queue(const NodeRec<PD, PR>& r, bool 
     }
 }
 
+// step_publish's stores, after the barrier behind sh.fm (the streamed pass folds that barrier into
+// its own and calls them itself): thread T < 2 kind T's flat maximum, thread 2 + L counter L
+// (kind L >> 1: one-step records, L & 1 = 0, or middle pieces) = cnt(L)
+template <int BS, class Cnt>
+__device__ __forceinline__ void step_publish_store(const StepShared& sh, const StepTables& st, int64_t blk, Cnt cnt) {
+    if (threadIdx.x < 2) st.flat[blk * 2 + threadIdx.x] = block_flat_max<BS>(sh, threadIdx.x);
+    else if (threadIdx.x < 6) st.cnt[blk * 4 + threadIdx.x - 2] = cnt((int)threadIdx.x - 2);
+}
 // Workgroup epilogue: the workgroup's flat-key maxima and record counts go to
 // its own slots (producer block blk) of the step tables (plain stores, no global atomics).  Every
 // thread calls it (barrier); sh.lc must have been zeroed before step_count.
@@ -519,16 +498,7 @@ __device__ __forceinline__ void step_publish(const StepSlots& o, StepShared& sh,
     wmax(0, o.flat0);
     wmax(1, o.flat1);
     __syncthreads();
-    if (threadIdx.x < 2) {
-        const int T = threadIdx.x;
-        int32_t m = sh.fm[T][0];
-#pragma unroll
-        for (int i = 1; i < BS / 64; ++i) m = max(m, sh.fm[T][i]);
-        st.flat[blk * 2 + T] = m;
-    } else if (threadIdx.x < 6) {
-        const int L = threadIdx.x - 2;
-        st.cnt[blk * 4 + L] = sh.lc[L >> 1][L & 1];
-    }
+    step_publish_store<BS>(sh, st, blk, [&](int L) { return sh.lc[L >> 1][L & 1]; });
 }
 
 // number of the n sorted records at a[] with bp <= t (upper bound)
@@ -540,6 +510,45 @@ __device__ __forceinline__ int32_t count_le(const Step1* a, int32_t n, int64_t t
         else hi = mid;
     }
     return lo;
+}
+
+// Prefix max of k1 (pm1) / suffix max of k0 (sm0) over a block's sorted one-step records, after
+// the barrier behind the sort: wave T scans kind T (a one-wave workgroup both in turn) in chunks of
+// 64 consecutive records, one per lane, with a carry.  L: the sorted records are srt[2][CAP] in
+// LDS and the maxima are also kept there, in pmL[2][CAP] and behind it smL[2][CAP], for the tile
+// rows; else the records are read from st.single.
+template <int BS, int CAP, bool L>
+__device__ __forceinline__ void step_scan_maxima(const Step1* srt, int32_t* pmL, const StepShared& sh,
+                                                 const StepTables& st, int64_t blk) {
+    const int n0 = sh.lc[0][0], n1 = sh.lc[1][0];
+    int32_t* smL = pmL + 2 * CAP;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int T = w; T < 2; T += (BS >= 128 ? 2 : 1)) {
+        const int n = T ? n1 : n0;
+        const int64_t base = s1_at(st, T, blk);
+        const Step1* a = L ? srt + T * CAP : st.single + base;
+        int32_t carry = -1;
+        for (int c0 = 0; c0 < n; c0 += 64) {
+            const int i = c0 + lane;
+            const int32_t v = max(wave_scan_max(i < n ? a[i].k1 : -1), carry);
+            if (i < n) {
+                st.pm1[base + i] = v;
+                if (L) pmL[T * CAP + i] = v;
+            }
+            carry = __builtin_amdgcn_readlane(v, 63);
+        }
+        // suffix maxima: lane l takes index c0 + 63 - l, so a prefix in lane order
+        carry = -1;
+        for (int c0 = (n - 1) & ~63; c0 >= 0 && n > 0; c0 -= 64) {
+            const int i = c0 + 63 - lane;
+            const int32_t v = max(wave_scan_max(i < n ? a[i].k0 : -1), carry);
+            if (i < n) {
+                st.sm0[base + i] = v;
+                if (L) smL[T * CAP + i] = v;
+            }
+            carry = __builtin_amdgcn_readlane(v, 63);
+        }
+    }
 }
 
 // After every Step1 record of the workgroup is in s1l (and a barrier): per pod kind,
@@ -586,38 +595,7 @@ __device__ __forceinline__ void step_sort_publish(Step1* s1l, Step1* srt, const 
         const int k = T ? i - n0 : i;
         st.single[s1_at(st, T, blk) + k] = srt[T * CAP + k];
     }
-    // prefix max of k1 / suffix max of k0: wave T scans kind T in chunks of 64 consecutive
-    // records (one per lane) with a carry; also kept in LDS (s1l is free now) for the rows
-    int32_t* pmL = reinterpret_cast<int32_t*>(s1l);  // [2][CAP]
-    int32_t* smL = pmL + 2 * CAP;                     // [2][CAP]
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    // wave T takes kind T (a one-wave workgroup takes both in turn)
-    for (int T = w; T < 2; T += (BS >= 128 ? 2 : 1)) {
-        const int n = T ? n1 : n0;
-        const Step1* a = srt + T * CAP;
-        const int64_t base = s1_at(st, T, blk);
-        int32_t carry = -1;
-        for (int c0 = 0; c0 < n; c0 += 64) {
-            const int i = c0 + lane;
-            const int32_t v = max(wave_scan_max(i < n ? a[i].k1 : -1), carry);
-            if (i < n) {
-                st.pm1[base + i] = v;
-                pmL[T * CAP + i] = v;
-            }
-            carry = __builtin_amdgcn_readlane(v, 63);
-        }
-        // suffix maxima: lane l takes index c0 + 63 - l, so a prefix in lane order
-        carry = -1;
-        for (int c0 = (n - 1) & ~63; c0 >= 0 && n > 0; c0 -= 64) {
-            const int i = c0 + 63 - lane;
-            const int32_t v = max(wave_scan_max(i < n ? a[i].k0 : -1), carry);
-            if (i < n) {
-                st.sm0[base + i] = v;
-                smL[T * CAP + i] = v;
-            }
-            carry = __builtin_amdgcn_readlane(v, 63);
-        }
-    }
+    step_scan_maxima<BS, CAP, true>(srt, reinterpret_cast<int32_t*>(s1l), sh, st, blk);  // (s1l is free now)
 }
 
 // The same for a block whose records exceed the LDS staging: staged in st.stage
@@ -639,26 +617,7 @@ __device__ __forceinline__ void step_sort_publish_global(const StepShared& sh, c
         st.single[s1_at(st, T, blk) + rank] = v;
     }
     __syncthreads();
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int T = w; T < 2; T += (BS >= 128 ? 2 : 1)) {
-        const int n = T ? n1 : n0;
-        const int64_t base = s1_at(st, T, blk);
-        const Step1* a = st.single + base;
-        int32_t carry = -1;
-        for (int c0 = 0; c0 < n; c0 += 64) {
-            const int i = c0 + lane;
-            const int32_t v = max(wave_scan_max(i < n ? a[i].k1 : -1), carry);
-            if (i < n) st.pm1[base + i] = v;
-            carry = __builtin_amdgcn_readlane(v, 63);
-        }
-        carry = -1;
-        for (int c0 = (n - 1) & ~63; c0 >= 0 && n > 0; c0 -= 64) {
-            const int i = c0 + 63 - lane;
-            const int32_t v = max(wave_scan_max(i < n ? a[i].k0 : -1), carry);
-            if (i < n) st.sm0[base + i] = v;
-            carry = __builtin_amdgcn_readlane(v, 63);
-        }
-    }
+    step_scan_maxima<BS, 0, false>(nullptr, nullptr, sh, st, blk);
 }
 
 // ---- middle pieces -> disjoint elementary pieces (per block and kind, after the emit)
@@ -785,13 +744,7 @@ __device__ __forceinline__ void step_tile_rows(const Step1* s1l, const Step1* sr
     const int32_t* pmL = reinterpret_cast<const int32_t*>(s1l);
     const int32_t* smL = pmL + 2 * CAP;
     __syncthreads();
-    int32_t fl[2];  // the block's flat maxima
-#pragma unroll
-    for (int T = 0; T < 2; ++T) {
-        fl[T] = sh.fm[T][0];
-#pragma unroll
-        for (int i = 1; i < BS / 64; ++i) fl[T] = max(fl[T], sh.fm[T][i]);
-    }
+    const int32_t fl[2] = {block_flat_max<BS>(sh, 0), block_flat_max<BS>(sh, 1)};
     // item i: tile i / 4, kind (i / 2) % 2, bound i % 2 (lo, hi): one LDS search each, the
     // four items of a tile on adjacent lanes combine by shuffles
     for (int i0 = 0; i0 < 4 * st.ntiles; i0 += BS) {
@@ -857,6 +810,30 @@ __device__ __forceinline__ void step_tile_rows(const Step1* s1l, const Step1* sr
             if (st.prow) st.prow[(int64_t)t * st.nblk + blk] = make_int2(pp, pp1);
         }
     }
+}
+
+// The producers' epilogue, after every one-step record and middle piece of the block is out (and
+// a barrier): sort + publish (stamp 6), and with st.rows the elementary pieces and the tile rows.
+// g1 (workgroup-uniform): the block's one-step records went through st.stage, else they are in
+// s1l[2][CAP].  pre: this thread's first tile bound when the caller loaded it early
+// (tile_prefetch), null: loaded here, behind the sort.  ps: the LDS the caller can lend the pieces.
+// Every thread of the BS calls it (barriers).
+template <int BS, int CAP>
+__device__ __forceinline__ void step_epilogue(bool g1, Step1* s1l, Step1* srt, StepShared& sh, const StepTables& st,
+                                              int64_t blk, const int64_t* pre, const PieceScr& ps,
+                                              unsigned long long* trace, int64_t wg) {
+    if (g1) step_sort_publish_global<BS>(sh, st, blk);
+    else step_sort_publish<BS, CAP>(s1l, srt, sh, st, blk);
+    CRANE_TSTAMP(trace, wg, 6);
+    if (!st.rows) return;
+    int64_t late = 0;
+    if (!pre) {
+        tile_prefetch(st, &late);
+        pre = &late;
+    }
+    step_pieces<BS>(sh, st, blk, ps);
+    if (g1) step_tile_rows<BS, CAP, true>(s1l, srt, sh, st, blk, pre, ps);
+    else step_tile_rows<BS, CAP, false>(s1l, srt, sh, st, blk, pre, ps);
 }
 
 // ---- step_sort_publish + step_tile_rows for a block of few one-step records, in registers.

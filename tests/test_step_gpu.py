@@ -135,6 +135,42 @@ def test_step_at_large_n():
         assert np.array_equal(out[i][0], out[0][0]) and np.array_equal(out[i][1], out[0][1]), i
 
 
+def _spec_8x8():
+    base = cd.default_policy_spec()
+    s = dict(base)
+    s["predicate"] = base["predicate"] + [("cpu_usage_max_avg_1d", 0.5), ("mem_usage_max_avg_1d", 0.0),
+                                          ("not_synced", 0.1), ("mem_usage_avg_5m", 0.3)]
+    return s
+
+
+@pytest.mark.parametrize("shape,n_nodes,n_pods,step_ns,ds_frac,seed", [
+    ("4x6", 257, 65, 1_000_000_000, 0.5, 3),    # a partial second block
+    ("8x8", 777, 90, 20_000_000_000, 0.1, 200),  # multi-step nodes, middle pieces
+    ("4x6", 1500, 4100, 60_000_000, 0.1, 210),  # 5 tiles: two rounds of tile-row items, pieces cut
+])
+def test_standalone_k3a_matches_fused(shape, n_nodes, n_pods, step_ns, ds_frac, seed):
+    """The stand-alone K3a (k3a_steps over records already written) builds the tables the fused or
+    streamed node pass builds: with clean records a keys-only eval runs it instead of K1 and gives
+    the same chosen nodes and scores, which are the oracle's."""
+    spec = _spec_8x8() if shape == "8x8" else cd.default_policy_spec()
+    c = synth.make_cluster(spec, n_nodes, n_pods, seed=seed, pod_step_ns=step_ns, ds_frac=ds_frac)
+    off, osc, och = oracle_soa(spec, c)
+    ok = (off < 0) | (c.ds != 0)[:, None]
+    ocs = np.where(ok, osc, -1).max(axis=1)
+    for rows in (1, 0):
+        for pc in (1, 2):
+            eng = engine_for(spec, c, opts={"step_rows": rows, "step_pieces": pc})
+            _, _, ch1, cs1 = eng.eval(c.now, c.ds)  # records dirty: K1 builds the tables
+            eng.eval(c.now, c.ds, matrix=True)      # writes the records
+            eng.set_profiling(True)
+            _, _, ch2, cs2 = eng.eval(c.now, c.ds)
+            names = [n for n, _ in eng.stage_times()]
+            eng.close()
+            assert "k3a_steps" in names and not any(n.startswith("k1_") for n in names), (rows, pc, names)
+            assert np.array_equal(ch2, ch1) and np.array_equal(cs2, cs1), (rows, pc)
+            assert np.array_equal(ch2, och) and np.array_equal(cs2, ocs), (rows, pc)
+
+
 def _oracle_hv(spec, c, now_ns):
     from oracle import oracle as O
     _, hv = O.hot_values(spec, c.b_node, c.b_ts, c.n_nodes, now_ns // 10**9)
