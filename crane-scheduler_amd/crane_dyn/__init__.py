@@ -136,6 +136,10 @@ def _load():
         "crane_dyn_step_keys_queue": (C.c_int, [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp]),
         "crane_dyn_forget_queue": (C.c_int, [vp, vp]),
         "crane_dyn_step_flush": (C.c_int, [vp]),
+        "crane_dyn_num_predicates": (C.c_int32, [vp]),
+        "crane_dyn_filter_counts_async": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp]),
+        "crane_dyn_filter_counts": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
+        "crane_dyn_group_filter_counts": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -171,6 +175,8 @@ ABI_SYMBOLS = (
     "crane_queue_create", "crane_queue_wait", "crane_queue_last_error", "crane_queue_destroy",
     "crane_queue_packets",
     "crane_dyn_step_keys_queue", "crane_dyn_forget_queue", "crane_dyn_step_flush",
+    "crane_dyn_num_predicates", "crane_dyn_filter_counts_async", "crane_dyn_filter_counts",
+    "crane_dyn_group_filter_counts",
 )
 
 
@@ -537,6 +543,50 @@ class Engine:
         self._check(lib.crane_dyn_eval_keys_async(self.h, P, C.c_void_p(d_now.data_ptr()),
                                                   None if d_flags is None else C.c_void_p(d_flags.data_ptr()),
                                                   C.c_void_p(d_keys.data_ptr()), stream))
+
+    @property
+    def n_pred(self):
+        """The policy's predicates, active or not: a filter_counts row has n_pred + 1 columns."""
+        return int(lib.crane_dyn_num_predicates(self.h))
+
+    def filter_counts(self, now_ns, pod_flags=None):
+        """Filter diagnosis (crane_dyn_filter_counts): int32 [P, n_pred + 1], per pod the shard's
+        nodes by first failing predicate (policy order) and, last, the nodes that pass."""
+        now = np.ascontiguousarray(now_ns, np.int64).reshape(-1)
+        P = len(now)
+        fl = None if pod_flags is None else np.ascontiguousarray(pod_flags, np.uint8).reshape(-1)
+        if fl is not None and len(fl) != P:
+            raise ValueError("pod_flags length mismatch")
+        out = np.empty((P, self.n_pred + 1), np.int32)
+        self._check(lib.crane_dyn_filter_counts(self.h, P, _ptr(now), _ptr(fl), _ptr(out)))
+        return out
+
+    def filter_counts_async(self, d_now, d_flags, d_counts, stream=None):
+        """d_now int64[P], d_flags uint8[P] or None, d_counts int32[P, n_pred + 1]: contiguous torch
+        tensors on the engine's device (ValueError otherwise); enqueued, not synchronised."""
+        import torch
+        P = d_now.numel()
+
+        def want(name, t, dtype, shape):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor")
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, not {t.dtype}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must have shape {shape}, not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError(f"{name} must be on device {self.device}, not {t.device}")
+
+        want("d_now", d_now, torch.int64, (P,))
+        if d_flags is not None:
+            want("d_flags", d_flags, torch.uint8, (P,))
+        want("d_counts", d_counts, torch.int32, (P, self.n_pred + 1))
+        self._ready(stream)
+        self._check(lib.crane_dyn_filter_counts_async(self.h, P, C.c_void_p(d_now.data_ptr()),
+                                                      None if d_flags is None else C.c_void_p(d_flags.data_ptr()),
+                                                      C.c_void_p(d_counts.data_ptr()), stream))
 
     def forget_stream(self, stream):
         """The caller is about to destroy `stream` (a raw hipStream_t handle): wait for it and drop
@@ -914,6 +964,18 @@ class Group:
         self._check(lib.crane_dyn_group_node_steps(self.h, int(t0_ns), int(t1_ns), N, _ptr(ns), _ptr(bp), _ptr(ff),
                                                    _ptr(sc)))
         return ns, bp, ff, sc
+
+    def filter_counts(self, now_ns, pod_flags=None):
+        """Engine.filter_counts over the whole cluster: the shards' rows summed, int32 [P, n_pred + 1]."""
+        now = np.ascontiguousarray(now_ns, np.int64).reshape(-1)
+        P = len(now)
+        fl = None if pod_flags is None else np.ascontiguousarray(pod_flags, np.uint8).reshape(-1)
+        if fl is not None and len(fl) != P:
+            raise ValueError("pod_flags length mismatch")
+        n_pred = int(lib.crane_dyn_num_predicates(lib.crane_dyn_group_engine(self.h, 0, 0)))
+        out = np.empty((P, n_pred + 1), np.int32)
+        self._check(lib.crane_dyn_group_filter_counts(self.h, P, _ptr(now), _ptr(fl), _ptr(out)))
+        return out
 
     def schedule(self, now_ns, hv_ts_ns, pods_now, pod_flags=None):
         """One batch from host arrays: (chosen global node [P], chosen score [P])."""

@@ -139,6 +139,8 @@ struct Options {
                               // which runs it in its first launch (crane_dyn_step_flush; the group sets it);
                               // 2: it leaves its K1 too, and a step is one launch (kernels.hpp StepOne):
                               // this batch's K2 + K3p, the previous batch's K1, K3s of the one before
+    int diag_slices = 0;      // filter diagnosis (diagnose.hip): node slices per pod tile, 0 = from the sizes,
+                              // k = k slices (clamped to the shard's 256-node blocks)
 };
 // Fixed launch shapes (round 6 removed their options; the A/B sweeps that chose them are in
 // profiles/ab/r03_k2_cold_*.txt and profiles/r05/config3_option_sweep_queues.txt)
@@ -240,6 +242,7 @@ struct crane_dyn {
     DevBuf<uint8_t> flags;
     DevBuf<long long> keys;
     DevBuf<int8_t> ff;
+    DevBuf<int32_t> dcounts;  // crane_dyn_filter_counts: the rows on the device
     DevBuf<int64_t> score;
     DevBuf<int8_t> score8;
     HostBuf<int8_t> stage8;
@@ -1219,7 +1222,7 @@ int crane_dyn_destroy(crane_dyn* h) {
     h->sd.reset();  // (the shard's inputs go with the last engine holding them)
     h->rec.release();
     h->buckets.release(); h->now.release(); h->flags.release();
-    h->keys.release(); h->ff.release(); h->score.release(); h->score8.release();
+    h->keys.release(); h->ff.release(); h->dcounts.release(); h->score.release(); h->score8.release();
     h->stage8.release(); h->stagek.release();
     h->k2_sorted.release(); h->hvc.release();
     h->gcnt.release(); h->gbase.release(); h->gchosen.release(); h->gleaf.release(); h->gflags.release();
@@ -1287,6 +1290,10 @@ int crane_dyn_set_option(crane_dyn* h, const char* name, int64_t value) {
     const std::string n = name;
     Options& o = h->opt;
     auto range = [&](int64_t lo, int64_t hi) { return value >= lo && value <= hi; };
+    if (n == "diag_slices" && range(0, 0x7FFFFFFF)) {
+        o.diag_slices = (int)value;
+        return CRANE_OK;  // (a launch shape of the diagnosis alone: nothing derived depends on it)
+    }
     if (n == "k2_form" && (value == 0 || value == 2 || value == 3)) o.k2_form = (int)value;
     else if (n == "keys_path" && range(0, 1)) o.keys_path = (int)value;
     else if (n == "greedy_form" && range(0, 1)) o.greedy_form = (int)value;
@@ -1550,6 +1557,65 @@ int crane_dyn_eval_matrix_async(crane_dyn* h, int64_t P, const int64_t* d_now, c
     int rc = matrix_locked(h, P, d_now, d_flags, reinterpret_cast<long long*>(d_keys), d_first_fail, d_score, false,
                            ld, st);
     return rc ? rc : mark_busy(h, st);
+}
+
+// The Filter diagnosis of a pod batch (diagnose.hip): reads the shard's SoA rows only — no
+// record, no hot-value state, no step table.
+static int filter_counts_locked(crane_dyn* h, int64_t P, const int64_t* d_now, const uint8_t* d_flags,
+                                int32_t* d_counts, hipStream_t st) {
+    if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before diagnosing pods");
+    if (h->N > 0x7FFFFFFFLL) return h->fail(CRANE_E_INVALID, "filter counts are int32: the shard has 2^31 nodes or more");
+    if (P == 0) return CRANE_OK;
+    DiagArgs a{};
+    a.pol = h->dp;
+    a.N = h->N;
+    a.P = P;
+    a.val = h->sd->val.p;
+    a.ts = h->sd->ts.p;
+    a.now = d_now;
+    a.flags = d_flags;
+    a.counts = d_counts;
+    a.n_pred = h->n_pred_policy;
+    std::memcpy(a.pred_orig, h->pred_orig, sizeof a.pred_orig);
+    HIPTRY(h, launch_filter_counts(a, h->opt.diag_slices, h->n_cu, st));
+    return CRANE_OK;
+}
+
+int32_t crane_dyn_num_predicates(const crane_dyn* h) { return h && h->N != -2 ? (int32_t)h->n_pred_policy : 0; }
+
+int crane_dyn_filter_counts_async(crane_dyn* h, int64_t P, const int64_t* d_now, const uint8_t* d_flags,
+                                  int32_t* d_counts, void* stream) {
+    if (!h) return CRANE_E_INVALID;
+    Locked lk(h);
+    if (lk.rc) return lk.rc;
+    if (P < 0 || (P > 0 && (!d_now || !d_counts))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    HIPTRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    int rc = filter_counts_locked(h, P, d_now, d_flags, d_counts, st);
+    return rc ? rc : mark_busy(h, st);
+}
+
+int crane_dyn_filter_counts(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8_t* pod_flags,
+                            int32_t* counts) {
+    if (!h) return CRANE_E_INVALID;
+    Locked lk(h);
+    if (lk.rc) return lk.rc;
+    if (P < 0 || (P > 0 && (!now_ns || !counts))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before diagnosing pods");
+    if (P == 0) return CRANE_OK;
+    HIPTRY(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;
+    const size_t cells = (size_t)P * (size_t)(h->n_pred_policy + 1);
+    HIPTRY(h, h->now.reserve((size_t)P));
+    HIPTRY(h, h->flags.reserve((size_t)P));
+    HIPTRY(h, h->dcounts.reserve(cells));
+    HIPTRY(h, hipMemcpyAsync(h->now.p, now_ns, sizeof(int64_t) * P, hipMemcpyHostToDevice, h->stream));
+    if (pod_flags) HIPTRY(h, hipMemcpyAsync(h->flags.p, pod_flags, P, hipMemcpyHostToDevice, h->stream));
+    if (int rc = filter_counts_locked(h, P, h->now.p, pod_flags ? h->flags.p : nullptr, h->dcounts.p, h->stream))
+        return rc;
+    HIPTRY(h, hipMemcpyAsync(counts, h->dcounts.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return CRANE_OK;
 }
 
 // kube-scheduler v1.23.3 numFeasibleNodesToFind (pkg/scheduler/core/generic_scheduler.go,

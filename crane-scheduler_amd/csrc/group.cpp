@@ -1106,6 +1106,26 @@ int crane_dyn_group_hot_values(crane_dyn_group* g, int64_t n, double* hv_out) {
     return CRANE_OK;
 }
 
+int crane_dyn_group_filter_counts(crane_dyn_group* g, int64_t n_pods, const int64_t* now_ns, const uint8_t* pod_flags,
+                                  int32_t* counts) {
+    if (!g) return CRANE_E_INVALID;
+    GLock lk(g);
+    if (int rc = check_ready(g)) return rc;
+    if (n_pods < 0 || (n_pods > 0 && (!now_ns || !counts))) return g->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (g->N > 0x7FFFFFFFLL) return g->fail(CRANE_E_INVALID, "filter counts are int32: the cluster has 2^31 nodes or more");
+    if (int rc = wait_all(g)) return rc;
+    // the shards' rows added on the host (the diagnosis path, not the timed one: no collective)
+    const size_t cells = (size_t)n_pods * (size_t)(crane_dyn_num_predicates(g->eng[0][0]) + 1);
+    std::vector<int32_t> part(cells);
+    std::fill(counts, counts + cells, 0);
+    for (int i = 0; i < g->n; ++i) {
+        crane_dyn* e = g->eng[0][(size_t)i];
+        if (int rc = crane_dyn_filter_counts(e, n_pods, now_ns, pod_flags, part.data())) return engine_err(g, e, rc, i);
+        for (size_t c = 0; c < cells; ++c) counts[c] += part[c];
+    }
+    return CRANE_OK;
+}
+
 int crane_dyn_group_node_steps(crane_dyn_group* g, int64_t t0_ns, int64_t t1_ns, int64_t n, uint8_t* n_steps,
                                int64_t* bp, int8_t* first_fail, int8_t* score) {
     if (!g) return CRANE_E_INVALID;

@@ -109,6 +109,25 @@ int node_step_slots(int shape);
 hipError_t launch_node_steps(int shape, const MatrixArgs& a, int64_t t0, int64_t t1, uint8_t* ns, int64_t* bp,
                              int8_t* ff, int8_t* sc, hipStream_t st, const int64_t* idx = nullptr);
 
+// Filter diagnosis (diagnose.hip, crane_dyn_filter_counts): per pod, the shard's nodes counted by
+// first failing predicate, counts[p * (n_pred + 1) + j] (j = policy predicate index; j = n_pred:
+// the feasible nodes).  Reads the SoA rows of the policy's predicates only.
+struct DiagArgs {
+    DevPolicy pol;
+    int64_t N, P;
+    const double* val;     // [M][N] shard SoA
+    const int64_t* ts;
+    const int64_t* now;    // [P]
+    const uint8_t* flags;  // [P] or null
+    int32_t* counts;       // [P][n_pred + 1]
+    int32_t n_pred;        // the policy's predicates, active or not
+    int32_t S;             // node slices per pod tile (set by the launch)
+    int8_t pred_orig[kMaxPred];  // device predicate -> policy predicate index (ascending)
+};
+// slices: 0 = chosen from the sizes and the device's n_cu compute units, k = k slices (clamped to
+// the shard's 256-node blocks).  Zeroes counts itself where the slices add into it.
+hipError_t launch_filter_counts(const DiagArgs& a, int slices, int n_cu, hipStream_t st);
+
 // Scatter update of k nodes' parsed annotations (crane_dyn_update_nodes, update.hip): the
 // staged columns go into the shard's SoA and, when the records are current, each changed
 // node's NodeRec is recomputed in place (the same rec_metrics / rec_hot_annotation as K1).

@@ -71,6 +71,15 @@ __device__ __forceinline__ void rec_metrics(const DevPolicy& pol, const int64_t 
     }
 }
 
+// Predicate k's expiry alone from its metric row (t, u): the e_pred[k] of rec_metrics, the same
+// expressions, for a pass that needs no record (the filter diagnosis, diagnose.hip).
+__device__ __forceinline__ int64_t pred_expiry(const DevPolicy& pol, int k, int64_t t, double u) {
+    const double lim = pol.pred_limit[k];
+    // isOverLoad (stats.go:94-112): usable (stats.go:51-76), limit != 0, u > limit
+    const bool over = t != kTsInvalid && !(u < 0.0) && lim != 0.0 && u > lim;
+    return over ? sat_add(t, pol.pred_dur[k]) : kTsInvalid;
+}
+
 // Hot-value part from the node_hot_value annotation (getNodeHotValue, stats.go:152-166:
 // no extra active period; an unusable or negative value counts as 0).
 template <int PD, int PR>

@@ -25,7 +25,8 @@
  * the calls that replace engine state (upload_nodes, update_nodes,
  * upload_bindings, binding_records, add_bindings, gc_bindings, destroy) and the
  * synchronous calls that run on the engine's own stream (eval, eval_compact,
- * node_steps, node_steps_subset, refresh_hot_values, hot_values, select, greedy)
+ * node_steps, node_steps_subset, refresh_hot_values, hot_values, select, greedy,
+ * filter_counts)
  * first wait for the caller streams this engine enqueued asynchronous work on
  * since the last such wait — those streams only, not the device — so they never
  * change a buffer a kernel is still reading.  The engine keeps a caller stream's
@@ -247,6 +248,30 @@ int crane_dyn_node_steps_subset(crane_dyn *h, int64_t t0_ns, int64_t t1_ns, int6
 int crane_dyn_eval_matrix_async(crane_dyn *h, int64_t n_pods, const int64_t *d_now_ns, const uint8_t *d_pod_flags,
                                 int8_t *d_first_fail, int8_t *d_score, int64_t ld, int64_t *d_keys, void *stream);
 
+/* Filter diagnosis of a pod batch: per pod, the shard's nodes counted by the Filter's verdict
+ * (DynamicScheduler.Filter, plugins.go:39-69) — for a pod that no node takes (key -1), what
+ * kube-scheduler's FitError reports as "0/N nodes are available: k ..." with one reason per
+ * overloaded predicate (plugins.go:59-66).  With n_pred = crane_dyn_num_predicates (the policy's
+ * predicate list, active or not):
+ *   counts[p*(n_pred+1) + j], j < n_pred: the nodes whose first_fail (as crane_dyn_eval) is j;
+ *                                         a predicate with no active duration keeps 0;
+ *   counts[p*(n_pred+1) + n_pred]       : the nodes that pass the Filter.
+ * A row sums to the shard's node count; a CRANE_POD_DAEMONSET pod has every node in the last
+ * column (plugins.go:41-43); rows of node shards add up to the cluster's.  The same numbers as a
+ * histogram of crane_dyn_eval_matrix_async's d_first_fail rows, without the n_pods x n_nodes
+ * matrix: one pass over the predicates' annotation rows per pod tile.  It reads the uploaded
+ * annotations only: hot values, node records and a step sequence around it are unaffected.
+ * A shim calls it for the pods of a batch that came back unschedulable and formats one row
+ * with the policy's predicate names.  CRANE_E_STATE before nodes are uploaded;
+ * n_pods = 0 is a no-op; shards of 2^31 nodes or more are rejected (int32 counts).
+ * _async: device pointers, enqueued on `stream` (NULL = engine stream), not synchronised;
+ * the other form takes host arrays and is synchronous. */
+int32_t crane_dyn_num_predicates(const crane_dyn *h);
+int crane_dyn_filter_counts_async(crane_dyn *h, int64_t n_pods, const int64_t *d_now_ns,
+                                  const uint8_t *d_pod_flags, int32_t *d_counts, void *stream);
+int crane_dyn_filter_counts(crane_dyn *h, int64_t n_pods, const int64_t *now_ns,
+                            const uint8_t *pod_flags, int32_t *counts);
+
 /* Framework-level selection for a pod queue, in order — what kube-scheduler
  * v1.23.3 (go.mod:26; pkg/scheduler/core/generic_scheduler.go, not in the
  * repo) does around the plugin with the shipped profile
@@ -370,6 +395,8 @@ const char *crane_dyn_version(void);
  *   "step_pieces" 0 auto | 1 | 2: middle pieces cut into elementary ones when it pays | always | never
  *   "step_lds_cap" one-step records per kind staged in K1's LDS at most (0: all through device memory)
  *   "sel_chain" 0 LDS rank/select walk of the selection windows (N <= 131072) | 1 streaming kernel
+ *   "diag_slices" 0 crane_dyn_filter_counts splits the nodes of a pod tile into slices by the sizes | k: into
+ *     k slices (clamped to the shard's 256-node blocks; 1: no atomics, one workgroup per pod tile)
  *   "trace" 0 | 1: phase stamps of the step kernels (crane_dyn_debug_trace) */
 int crane_dyn_set_option(crane_dyn *h, const char *name, int64_t value);
 /* Phase stamps of the last K2x (which = 0), K1 (1) or K3s (2) launch with option
@@ -459,7 +486,11 @@ int crane_dyn_group_sync(crane_dyn_group *g);
  *   binding_records / add_bindings / gc_bindings / binding_count = the BindingRecords heap
  *     (binding.go:50-123) with global node indices: every device runs the same heap (its order
  *     depends on timestamps only) with the other shards' nodes as "no node";
- *   refresh_hot_values / hot_values / node_steps = per shard, results at the global rows.
+ *   refresh_hot_values / hot_values / node_steps = per shard, results at the global rows;
+ *   filter_counts = crane_dyn_filter_counts of every shard, the rows summed on the host (the
+ *     diagnosis of unschedulable pods, not the timed path: no collective); n_pred =
+ *     crane_dyn_num_predicates of any of the group's engines; clusters of 2^31 nodes or more
+ *     are rejected.
  * Synchronous; each first waits for the group's batches in flight. */
 int crane_dyn_group_update_nodes(crane_dyn_group *g, int64_t k, const int64_t *idx, const double *val,
                                  const int64_t *ts, const double *hv, const int64_t *hv_ts);
@@ -474,6 +505,8 @@ int crane_dyn_group_gc_bindings(crane_dyn_group *g, int64_t now_ns);
 int64_t crane_dyn_group_binding_count(crane_dyn_group *g);
 int crane_dyn_group_refresh_hot_values(crane_dyn_group *g, int64_t now_ns, int64_t hv_ts_ns);
 int crane_dyn_group_hot_values(crane_dyn_group *g, int64_t n, double *hv_out);
+int crane_dyn_group_filter_counts(crane_dyn_group *g, int64_t n_pods, const int64_t *now_ns,
+                                  const uint8_t *pod_flags, int32_t *counts);
 int crane_dyn_group_node_steps(crane_dyn_group *g, int64_t t0_ns, int64_t t1_ns, int64_t n, uint8_t *n_steps,
                                int64_t *bp, int8_t *first_fail, int8_t *score);
 /* One batch from host arrays, synchronous: chosen[p] = global node index or -1, chosen_score[p]
