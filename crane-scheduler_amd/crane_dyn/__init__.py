@@ -140,6 +140,10 @@ def _load():
         "crane_dyn_filter_counts_async": (C.c_int, [vp, C.c_int64, vp, vp, vp, vp]),
         "crane_dyn_filter_counts": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
         "crane_dyn_group_filter_counts": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
+        "crane_dyn_topk_async": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int32, vp, vp]),
+        "crane_dyn_topk": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int32, vp]),
+        "crane_topk_merge": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, P(vp), vp]),
+        "crane_dyn_group_topk": (C.c_int, [vp, C.c_int64, vp, vp, C.c_int32, vp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -177,6 +181,7 @@ ABI_SYMBOLS = (
     "crane_dyn_step_keys_queue", "crane_dyn_forget_queue", "crane_dyn_step_flush",
     "crane_dyn_num_predicates", "crane_dyn_filter_counts_async", "crane_dyn_filter_counts",
     "crane_dyn_group_filter_counts",
+    "crane_dyn_topk_async", "crane_dyn_topk", "crane_topk_merge", "crane_dyn_group_topk",
 )
 
 
@@ -390,6 +395,24 @@ def key_node(key: int):
     return n, s.value
 
 
+TOPK_MAX = 16  # CRANE_TOPK_MAX
+
+
+def topk_merge(lists):
+    """The k largest keys per pod of several [P, k] top-k arrays (Engine.topk rows of node shards:
+    descending, -1 padded, global node indices), in the same format (crane_topk_merge, host only)."""
+    arrs = [np.ascontiguousarray(a, np.int64) for a in lists]
+    if not arrs or arrs[0].ndim != 2 or any(a.shape != arrs[0].shape for a in arrs):
+        raise ValueError("topk_merge takes one or more [P, k] arrays of one shape")
+    n_pods, k = arrs[0].shape
+    out = np.empty((n_pods, k), np.int64)
+    rows = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+    rc = lib.crane_topk_merge(len(arrs), n_pods, k, rows, _ptr(out))
+    if rc:
+        raise CraneError(rc, f"top-k merge of {len(arrs)} lists, k = {k}")
+    return out
+
+
 # ------------------------------------------------------------------ engine
 class Engine:
     """One engine = one node shard on one HIP device (crane_dyn_create)."""
@@ -587,6 +610,46 @@ class Engine:
         self._check(lib.crane_dyn_filter_counts_async(self.h, P, C.c_void_p(d_now.data_ptr()),
                                                       None if d_flags is None else C.c_void_p(d_flags.data_ptr()),
                                                       C.c_void_p(d_counts.data_ptr()), stream))
+
+    def topk(self, now_ns, pod_flags=None, k=8):
+        """The k best feasible nodes per pod (crane_dyn_topk): int64 [P, k], row p the pod's keys
+        (eval_keys_async's packing, key_node decodes) best first, -1 past its last feasible node."""
+        now = np.ascontiguousarray(now_ns, np.int64).reshape(-1)
+        P = len(now)
+        fl = None if pod_flags is None else np.ascontiguousarray(pod_flags, np.uint8).reshape(-1)
+        if fl is not None and len(fl) != P:
+            raise ValueError("pod_flags length mismatch")
+        k = int(k)
+        out = np.empty((P, max(k, 0)), np.int64)
+        self._check(lib.crane_dyn_topk(self.h, P, _ptr(now), _ptr(fl), k, _ptr(out)))
+        return out
+
+    def topk_async(self, d_now, d_flags, d_keys, stream=None):
+        """d_now int64[P], d_flags uint8[P] or None, d_keys int64[P, k] (k from its shape): contiguous
+        torch tensors on the engine's device (ValueError otherwise); enqueued, not synchronised."""
+        import torch
+        P = d_now.numel() if isinstance(d_now, torch.Tensor) else -1
+
+        def want(name, t, dtype, shape):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name} must be a torch tensor")
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, not {t.dtype}")
+            if t.dim() != len(shape) or any(b is not None and a != b for a, b in zip(t.shape, shape)):
+                raise ValueError(f"{name} must have shape {shape}, not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError(f"{name} must be on device {self.device}, not {t.device}")
+
+        want("d_now", d_now, torch.int64, (P,))
+        if d_flags is not None:
+            want("d_flags", d_flags, torch.uint8, (P,))
+        want("d_keys", d_keys, torch.int64, (P, None))  # (any k: the engine checks its range)
+        self._ready(stream)
+        self._check(lib.crane_dyn_topk_async(self.h, P, C.c_void_p(d_now.data_ptr()),
+                                             None if d_flags is None else C.c_void_p(d_flags.data_ptr()),
+                                             int(d_keys.shape[1]), C.c_void_p(d_keys.data_ptr()), stream))
 
     def forget_stream(self, stream):
         """The caller is about to destroy `stream` (a raw hipStream_t handle): wait for it and drop
@@ -975,6 +1038,18 @@ class Group:
         n_pred = int(lib.crane_dyn_num_predicates(lib.crane_dyn_group_engine(self.h, 0, 0)))
         out = np.empty((P, n_pred + 1), np.int32)
         self._check(lib.crane_dyn_group_filter_counts(self.h, P, _ptr(now), _ptr(fl), _ptr(out)))
+        return out
+
+    def topk(self, now_ns, pod_flags=None, k=8):
+        """Engine.topk over the whole cluster: the shards' rows merged on the host, int64 [P, k]."""
+        now = np.ascontiguousarray(now_ns, np.int64).reshape(-1)
+        P = len(now)
+        fl = None if pod_flags is None else np.ascontiguousarray(pod_flags, np.uint8).reshape(-1)
+        if fl is not None and len(fl) != P:
+            raise ValueError("pod_flags length mismatch")
+        k = int(k)
+        out = np.empty((P, max(k, 0)), np.int64)
+        self._check(lib.crane_dyn_group_topk(self.h, P, _ptr(now), _ptr(fl), k, _ptr(out)))
         return out
 
     def schedule(self, now_ns, hv_ts_ns, pods_now, pod_flags=None):

@@ -141,6 +141,8 @@ struct Options {
                               // this batch's K2 + K3p, the previous batch's K1, K3s of the one before
     int diag_slices = 0;      // filter diagnosis (diagnose.hip): node slices per pod tile, 0 = from the sizes,
                               // k = k slices (clamped to the shard's 256-node blocks)
+    int topk_slices = 0;      // top-k candidates (topk.hip): node slices per pod chunk, 0 = from the sizes,
+                              // s = s slices (clamped to the blocks), 1 = no second phase
 };
 // Fixed launch shapes (round 6 removed their options; the A/B sweeps that chose them are in
 // profiles/ab/r03_k2_cold_*.txt and profiles/r05/config3_option_sweep_queues.txt)
@@ -243,6 +245,8 @@ struct crane_dyn {
     DevBuf<long long> keys;
     DevBuf<int8_t> ff;
     DevBuf<int32_t> dcounts;  // crane_dyn_filter_counts: the rows on the device
+    DevBuf<long long> tkeys;  // crane_dyn_topk: the rows on the device
+    DevBuf<long long> tkpart; // ... and the slices' rows [P][S][k] of its first phase
     DevBuf<int64_t> score;
     DevBuf<int8_t> score8;
     HostBuf<int8_t> stage8;
@@ -1222,7 +1226,7 @@ int crane_dyn_destroy(crane_dyn* h) {
     h->sd.reset();  // (the shard's inputs go with the last engine holding them)
     h->rec.release();
     h->buckets.release(); h->now.release(); h->flags.release();
-    h->keys.release(); h->ff.release(); h->dcounts.release(); h->score.release(); h->score8.release();
+    h->keys.release(); h->ff.release(); h->dcounts.release(); h->tkeys.release(); h->tkpart.release(); h->score.release(); h->score8.release();
     h->stage8.release(); h->stagek.release();
     h->k2_sorted.release(); h->hvc.release();
     h->gcnt.release(); h->gbase.release(); h->gchosen.release(); h->gleaf.release(); h->gflags.release();
@@ -1293,6 +1297,10 @@ int crane_dyn_set_option(crane_dyn* h, const char* name, int64_t value) {
     if (n == "diag_slices" && range(0, 0x7FFFFFFF)) {
         o.diag_slices = (int)value;
         return CRANE_OK;  // (a launch shape of the diagnosis alone: nothing derived depends on it)
+    }
+    if (n == "topk_slices" && range(0, 0x7FFFFFFF)) {
+        o.topk_slices = (int)value;
+        return CRANE_OK;  // (a launch shape of the top-k pass alone)
     }
     if (n == "k2_form" && (value == 0 || value == 2 || value == 3)) o.k2_form = (int)value;
     else if (n == "keys_path" && range(0, 1)) o.keys_path = (int)value;
@@ -1614,6 +1622,73 @@ int crane_dyn_filter_counts(crane_dyn* h, int64_t P, const int64_t* now_ns, cons
     if (int rc = filter_counts_locked(h, P, h->now.p, pod_flags ? h->flags.p : nullptr, h->dcounts.p, h->stream))
         return rc;
     HIPTRY(h, hipMemcpyAsync(counts, h->dcounts.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return CRANE_OK;
+}
+
+// The k best feasible nodes per pod (topk.hip): the records' evaluation of the per-pair kernel,
+// ranked in the kernel instead of written out.
+static int topk_locked(crane_dyn* h, int64_t P, const int64_t* d_now, const uint8_t* d_flags, int32_t k,
+                       long long* d_keys, hipStream_t st) {
+    if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before ranking pods' candidates");
+    if (P == 0) return CRANE_OK;
+    if (h->rec_dirty) {
+        int rc = node_pass_locked(h, st);
+        if (rc) return rc;
+    }
+    const int64_t S = topk_slices(P, h->N, k, h->opt.topk_slices, h->n_cu);
+    if (S < 0)
+        return h->fail(CRANE_E_INVALID, "topk_slices leaves node slices of more than 2^24 nodes (or too many workgroups)");
+    if (S > 1) HIPTRY(h, h->tkpart.grow((size_t)P * (size_t)S * (size_t)k));
+    TopkArgs a{};
+    a.rec = h->rec.p;
+    a.N = h->N;
+    a.node_offset = h->node_offset;
+    a.now = d_now;
+    a.flags = d_flags;
+    a.P = P;
+    a.wsum = h->dp.wsum;
+    a.noprio = h->dp.noprio;
+    a.k = k;
+    a.S = (int32_t)S;
+    a.out = d_keys;
+    a.partial = S > 1 ? h->tkpart.p : nullptr;
+    HIPTRY(h, launch_topk(h->shape, a, st));
+    return CRANE_OK;
+}
+
+int crane_dyn_topk_async(crane_dyn* h, int64_t P, const int64_t* d_now, const uint8_t* d_flags, int32_t k,
+                         int64_t* d_keys, void* stream) {
+    if (!h) return CRANE_E_INVALID;
+    Locked lk(h);
+    if (lk.rc) return lk.rc;
+    if (P < 0 || (P > 0 && (!d_now || !d_keys))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (k < 1 || k > CRANE_TOPK_MAX) return h->fail(CRANE_E_INVALID, "k must be in [1, CRANE_TOPK_MAX]");
+    HIPTRY(h, hipSetDevice(h->device));
+    hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    int rc = topk_locked(h, P, d_now, d_flags, k, reinterpret_cast<long long*>(d_keys), st);
+    return rc ? rc : mark_busy(h, st);
+}
+
+int crane_dyn_topk(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8_t* pod_flags, int32_t k,
+                   int64_t* keys) {
+    if (!h) return CRANE_E_INVALID;
+    Locked lk(h);
+    if (lk.rc) return lk.rc;
+    if (P < 0 || (P > 0 && (!now_ns || !keys))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (k < 1 || k > CRANE_TOPK_MAX) return h->fail(CRANE_E_INVALID, "k must be in [1, CRANE_TOPK_MAX]");
+    if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before ranking pods' candidates");
+    if (P == 0) return CRANE_OK;
+    HIPTRY(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;
+    const size_t cells = (size_t)P * (size_t)k;
+    HIPTRY(h, h->now.reserve((size_t)P));
+    HIPTRY(h, h->flags.reserve((size_t)P));
+    HIPTRY(h, h->tkeys.reserve(cells));
+    HIPTRY(h, hipMemcpyAsync(h->now.p, now_ns, sizeof(int64_t) * P, hipMemcpyHostToDevice, h->stream));
+    if (pod_flags) HIPTRY(h, hipMemcpyAsync(h->flags.p, pod_flags, P, hipMemcpyHostToDevice, h->stream));
+    if (int rc = topk_locked(h, P, h->now.p, pod_flags ? h->flags.p : nullptr, k, h->tkeys.p, h->stream)) return rc;
+    HIPTRY(h, hipMemcpyAsync(keys, h->tkeys.p, sizeof(long long) * cells, hipMemcpyDeviceToHost, h->stream));
     HIPTRY(h, hipStreamSynchronize(h->stream));
     return CRANE_OK;
 }

@@ -1126,6 +1126,27 @@ int crane_dyn_group_filter_counts(crane_dyn_group* g, int64_t n_pods, const int6
     return CRANE_OK;
 }
 
+int crane_dyn_group_topk(crane_dyn_group* g, int64_t n_pods, const int64_t* now_ns, const uint8_t* pod_flags, int32_t k,
+                         int64_t* keys) {
+    if (!g) return CRANE_E_INVALID;
+    GLock lk(g);
+    if (int rc = check_ready(g)) return rc;
+    if (n_pods < 0 || (n_pods > 0 && (!now_ns || !keys))) return g->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (k < 1 || k > CRANE_TOPK_MAX) return g->fail(CRANE_E_INVALID, "k must be in [1, CRANE_TOPK_MAX]");
+    if (int rc = wait_all(g)) return rc;
+    // the shards' rows gathered and merged on the host (lists do not max-reduce: no collective)
+    const size_t cells = (size_t)n_pods * (size_t)k;
+    std::vector<std::vector<int64_t>> part((size_t)g->n, std::vector<int64_t>(cells));
+    std::vector<const int64_t*> rows((size_t)g->n);
+    for (int i = 0; i < g->n; ++i) {
+        crane_dyn* e = g->eng[0][(size_t)i];
+        if (int rc = crane_dyn_topk(e, n_pods, now_ns, pod_flags, k, part[(size_t)i].data())) return engine_err(g, e, rc, i);
+        rows[(size_t)i] = part[(size_t)i].data();
+    }
+    if (crane_topk_merge(g->n, n_pods, k, rows.data(), keys)) return g->fail(CRANE_E_INVALID, "top-k merge");
+    return CRANE_OK;
+}
+
 int crane_dyn_group_node_steps(crane_dyn_group* g, int64_t t0_ns, int64_t t1_ns, int64_t n, uint8_t* n_steps,
                                int64_t* bp, int8_t* first_fail, int8_t* score) {
     if (!g) return CRANE_E_INVALID;

@@ -128,6 +128,28 @@ struct DiagArgs {
 // the shard's 256-node blocks).  Zeroes counts itself where the slices add into it.
 hipError_t launch_filter_counts(const DiagArgs& a, int slices, int n_cu, hipStream_t st);
 
+// Top-k candidates (topk.hip, crane_dyn_topk): per pod the k largest keys of the shard's feasible
+// nodes, out[p * k + j] descending ((score << 32) | (0xFFFFFFFF - global node), -1 past the last).
+struct TopkArgs {
+    const void* rec;        // NodeRec [N]
+    int64_t N, node_offset;
+    const int64_t* now;     // [P]
+    const uint8_t* flags;   // [P] or null
+    int64_t P;
+    double wsum;
+    int32_t noprio;
+    int32_t k;              // 1 .. 16
+    int32_t S;              // node slices per pod chunk (topk_slices)
+    int32_t pad;
+    long long* out;         // [P][k]
+    long long* partial;     // [P][S][k] scratch of the slices' rows (S > 1), else null
+};
+// The slice count of a launch: slices 0 = chosen from the sizes and the device's n_cu compute units,
+// s = s slices (clamped to the shard's 256-node blocks); -1: a forced count leaves slices of more
+// than 2^24 nodes (the list keys' index bits), or the grid is too large.
+int64_t topk_slices(int64_t P, int64_t N, int k, int slices, int n_cu);
+hipError_t launch_topk(int shape, const TopkArgs& a, hipStream_t st);
+
 // Scatter update of k nodes' parsed annotations (crane_dyn_update_nodes, update.hip): the
 // staged columns go into the shard's SoA and, when the records are current, each changed
 // node's NodeRec is recomputed in place (the same rec_metrics / rec_hot_annotation as K1).

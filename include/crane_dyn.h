@@ -26,7 +26,7 @@
  * upload_bindings, binding_records, add_bindings, gc_bindings, destroy) and the
  * synchronous calls that run on the engine's own stream (eval, eval_compact,
  * node_steps, node_steps_subset, refresh_hot_values, hot_values, select, greedy,
- * filter_counts)
+ * filter_counts, topk)
  * first wait for the caller streams this engine enqueued asynchronous work on
  * since the last such wait — those streams only, not the device — so they never
  * change a buffer a kernel is still reading.  The engine keeps a caller stream's
@@ -272,6 +272,40 @@ int crane_dyn_filter_counts_async(crane_dyn *h, int64_t n_pods, const int64_t *d
 int crane_dyn_filter_counts(crane_dyn *h, int64_t n_pods, const int64_t *now_ns,
                             const uint8_t *pod_flags, int32_t *counts);
 
+/* The k best feasible nodes of every pod of a batch, 1 <= k <= CRANE_TOPK_MAX: row p holds
+ * keys[p*k + j], j = 0 .. k-1, the pod's j-th best node of the shard, packed exactly as
+ * crane_dyn_eval_keys_async packs its one key, (score << 32) | (0xFFFFFFFF - global node index)
+ * (node_offset included; crane_dyn_key_node decodes).  "Feasible" and "score" are those of
+ * crane_dyn_eval: Filter Success — or any node for a CRANE_POD_DAEMONSET pod — and the clamped
+ * Score.  Highest score first, the lowest index among equal scores: keys are distinct, a row is
+ * strictly descending, and a pod with fewer than k feasible nodes has -1 in the remaining places.
+ * So column 0 is crane_dyn_eval_keys_async's key, the first k' columns of a k-row are the k'-row,
+ * and a row's non-negative entries number min(k, feasible) with `feasible` the last column of
+ * crane_dyn_filter_counts.  All of it bit-exact against the per-pair evaluation, with no
+ * n_pods x n_nodes matrix: n_pods * k * 8 bytes are written.  A scheduler takes a pod's next
+ * candidate from its row when several pods of a batch chose one node, or a bind was refused,
+ * instead of evaluating again.
+ * CRANE_E_INVALID for k outside [1, CRANE_TOPK_MAX] or bad pointers, CRANE_E_STATE before nodes are
+ * uploaded; n_pods = 0 is a no-op.  The node records are current when it runs (hot values of the last
+ * refresh included), and pending deferred stages of a step sequence run first, so the sequence
+ * around the call returns the same keys.  Engine option "topk_slices" forces the node slices per
+ * pod chunk; a forced count that leaves slices of more than 2^24 nodes is CRANE_E_INVALID (the
+ * automatic count never does).
+ * _async: device pointers, enqueued on `stream` (NULL = engine stream), not synchronised; the
+ * other form takes host arrays and is synchronous. */
+#define CRANE_TOPK_MAX 16
+int crane_dyn_topk_async(crane_dyn *h, int64_t n_pods, const int64_t *d_now_ns, const uint8_t *d_pod_flags,
+                         int32_t k, int64_t *d_keys /* [n_pods][k] */, void *stream);
+int crane_dyn_topk(crane_dyn *h, int64_t n_pods, const int64_t *now_ns, const uint8_t *pod_flags,
+                   int32_t k, int64_t *keys /* host, [n_pods][k] */);
+/* The combine of node shards' top-k rows, plain host code (no device, no engine): each of the
+ * n_lists (>= 1) inputs is an [n_pods][k] array in the format above (descending, -1 padded, global
+ * node indices; rows of disjoint shards share no key), out[p*k + j] the k largest of their rows p
+ * in the same format.  out aliases no input.  A max all-reduce cannot merge lists: processes
+ * that hold node shards gather their rows and call this.  CRANE_E_INVALID for k outside
+ * [1, CRANE_TOPK_MAX], n_lists < 1, n_pods < 0 or a NULL pointer (with n_pods > 0). */
+int crane_topk_merge(int32_t n_lists, int64_t n_pods, int32_t k, const int64_t *const *lists, int64_t *out);
+
 /* Framework-level selection for a pod queue, in order — what kube-scheduler
  * v1.23.3 (go.mod:26; pkg/scheduler/core/generic_scheduler.go, not in the
  * repo) does around the plugin with the shipped profile
@@ -397,6 +431,8 @@ const char *crane_dyn_version(void);
  *   "sel_chain" 0 LDS rank/select walk of the selection windows (N <= 131072) | 1 streaming kernel
  *   "diag_slices" 0 crane_dyn_filter_counts splits the nodes of a pod tile into slices by the sizes | k: into
  *     k slices (clamped to the shard's 256-node blocks; 1: no atomics, one workgroup per pod tile)
+ *   "topk_slices" 0 crane_dyn_topk splits the nodes of a pod chunk into slices by the sizes | s: into s
+ *     slices (clamped to the shard's 256-node blocks; 1: one phase, no partial rows)
  *   "trace" 0 | 1: phase stamps of the step kernels (crane_dyn_debug_trace) */
 int crane_dyn_set_option(crane_dyn *h, const char *name, int64_t value);
 /* Phase stamps of the last K2x (which = 0), K1 (1) or K3s (2) launch with option
@@ -490,7 +526,9 @@ int crane_dyn_group_sync(crane_dyn_group *g);
  *   filter_counts = crane_dyn_filter_counts of every shard, the rows summed on the host (the
  *     diagnosis of unschedulable pods, not the timed path: no collective); n_pred =
  *     crane_dyn_num_predicates of any of the group's engines; clusters of 2^31 nodes or more
- *     are rejected.
+ *     are rejected;
+ *   topk = crane_dyn_topk of every shard, the shards' rows merged on the host with
+ *     crane_topk_merge (global node indices; no collective, like filter_counts).
  * Synchronous; each first waits for the group's batches in flight. */
 int crane_dyn_group_update_nodes(crane_dyn_group *g, int64_t k, const int64_t *idx, const double *val,
                                  const int64_t *ts, const double *hv, const int64_t *hv_ts);
@@ -507,6 +545,8 @@ int crane_dyn_group_refresh_hot_values(crane_dyn_group *g, int64_t now_ns, int64
 int crane_dyn_group_hot_values(crane_dyn_group *g, int64_t n, double *hv_out);
 int crane_dyn_group_filter_counts(crane_dyn_group *g, int64_t n_pods, const int64_t *now_ns,
                                   const uint8_t *pod_flags, int32_t *counts);
+int crane_dyn_group_topk(crane_dyn_group *g, int64_t n_pods, const int64_t *now_ns, const uint8_t *pod_flags,
+                         int32_t k, int64_t *keys);
 int crane_dyn_group_node_steps(crane_dyn_group *g, int64_t t0_ns, int64_t t1_ns, int64_t n, uint8_t *n_steps,
                                int64_t *bp, int8_t *first_fail, int8_t *score);
 /* One batch from host arrays, synchronous: chosen[p] = global node index or -1, chosen_score[p]
