@@ -16,6 +16,24 @@ namespace crane {
 
 // Go int(float64) on amd64 (CVTTSD2SQ): NaN and out-of-range -> INT64_MIN.
 // Used by stats.go:135 (int(score/weight)) and plugins.go:91 (int(hv*10)).
+//
+// The conversion, the wrapping int64 subtraction after it (plugins.go:91) and the clamp
+// (NormalizeScore, utils.go:58-68) are stated in five places, each behind other kernels; a change
+// to one is a change to all (tests/test_value_edges_gpu.py drives each with NaN, +-Inf and huge
+// inputs against the oracle):
+//  1. go_int here: the penalty int(hv * 10) of rec_hot_annotation and rec_hot_counts, i.e. of
+//     every NodeRec (K1 in kernels.hip, the streamed K1, the scatter update in update.hip).
+//  2. score_of_sum (step_node.hpp): the base int(s / wsum) with a one-instruction path for
+//     |q| < 2^31 beside the full conversion, then base - pen wrapping and the clamp.  Through
+//     score_at it is the score of the per-pair kernel and the answer tables (matrix.hip), the
+//     step path (step.hip, k1stream_body.hpp), topk.hip and select.hip.
+//  3. go_int_g and final_score (greedy.hip): base and penalty of the sequential greedy kernel,
+//     the penalty recomputed from the window counts after every placement.
+//  4. RunIter::next (merge.hip): base - 10 v in plain int64, no wrap — valid because M1 raises
+//     its flag for any base below INT64_MIN + 2^40 (int(NaN), overflow) and crane_dyn_greedy
+//     then runs the sequential kernel instead.
+//  5. On the host, go_seconds_trunc (engine.hip) and seconds_trunc (bindings.hpp):
+//     int64(d.Seconds()) of binding.go:85, the same range test.
 __device__ __forceinline__ int64_t go_int(double x) {
     if (!(x >= -9223372036854775808.0 && x < 9223372036854775808.0)) return INT64_MIN;
     return (int64_t)x;

@@ -57,6 +57,51 @@ def policy_json(pol):
             "hotValue": [[t, c] for t, c in pol["hotValue"]]}
 
 
+def value_edge_kats(D):
+    """Usages and hot values outside what the controller writes (tests/test_value_edges*.py run
+    the same classes through every consumer).  Every metric fresh at 0.1 unless stated: each term
+    is (1 - 0.1) * w * 100 = 90 w, the weights sum to 2.0, so the base score is 180 / 2 = 90, and
+    162 / 2 = 81 without the cpu_usage_avg_5m term (weight 0.2)."""
+    ks = []
+    u = [0.1] * 6
+    ks.append(kat("VE-nan-hv0", anno_of(["NaN"] + u[1:], hv=0), -1, 0,
+                  note="NaN > 0.65 is false: passes; int(NaN) = INT64_MIN, - int(0 * 10) = INT64_MIN -> clamp 0"))
+    ks.append(kat("VE-1e300-hv0.7", anno_of(["1e300"] + u[1:], hv=0.7), 0, 100,
+                  note="term (1 - 1e300) * 0.2 * 100 = -2e301, q = -1e301 out of int64 -> INT64_MIN; "
+                       "- int(0.7 * 10) = 7 wraps to INT64_MAX - 6 -> clamp 100 (what a DaemonSet pod sees)"))
+    ks.append(kat("VE-1e17-hvnan", anno_of(["1e17"] + u[1:], hv="NaN"), 0, 100,
+                  note="q = (-2e18 + 162) / 2 ~ -1e18 fits int64; int(NaN * 10) = INT64_MIN; "
+                       "-1e18 - INT64_MIN ~ +8.2e18 -> clamp 100"))
+    ks.append(kat("VE-hvnan", anno_of(u, hv="NaN"), -1, 0,
+                  note="NaN < 0 is false: the hot value is used; 90 - INT64_MIN wraps to INT64_MIN + 90 -> clamp 0"))
+    ks.append(kat("VE-hv1.26", anno_of(u, hv=1.26), -1, 78, note="int(1.26 * 10) = int(12.6) = 12; 90 - 12"))
+    ks.append(kat("VE-hv0.05", anno_of(u, hv=0.05), -1, 90, note="int(0.5) = 0"))
+    ks.append(kat("VE-hv0.15", anno_of(u, hv=0.15), -1, 89, note="int(1.5) = 1"))
+    ks.append(kat("VE-hv-negzero", anno_of(u, hv="-0.0"), -1, 90, note="-0 < 0 is false: used; int(-0 * 10) = 0"))
+    ks.append(kat("VE-hv-neginf", anno_of(u, hv="-Inf"), -1, 90,
+                  note="-Inf < 0: rejected, the hot value counts as 0 (used, it would be INT64_MIN -> 0)"))
+    ks.append(kat("VE-hv9.3e17", anno_of(u, hv="9.3e17"), -1, 0,
+                  note="9.3e18 >= 2^63: the conversion is out of range -> INT64_MIN; 90 - INT64_MIN wraps negative"))
+    ks.append(kat("VE-hv9.2e17", anno_of(u, hv="9.2e17"), -1, 0, note="9.2e18 < 2^63 converts; 90 - 9.2e18 < 0, no wrap"))
+    ks.append(kat("VE-1e17-hv9.2e17", anno_of(["1e17"] + u[1:], hv="9.2e17"), 0, 100,
+                  note="-1e18 - 9.2e18 = -1.02e19 < -2^63 wraps to about +8.2e18 -> clamp 100"))
+    ks.append(kat("VE-over-hvinf", anno_of([1.5] * 6, hv="+Inf"), 0, 100,
+                  note="KAT-5's node (q = -50): int(+Inf) = INT64_MIN; -50 - INT64_MIN = 2^63 - 50 fits -> clamp 100"))
+    ks.append(kat("VE-neginf", anno_of(["-Inf"] + u[1:]), -1, 81,
+                  note="-Inf < 0: rejected like any negative usage (term 0, weight counted), where +Inf fails the Filter"))
+    ks.append(kat("VE-denormal", anno_of(["5e-324"] + u[1:]), -1, 91, note="1 - 5e-324 = 1: term 20, (20 + 162) / 2"))
+    ks.append(kat("VE-negzero", anno_of(["-0.0"] + u[1:]), -1, 91, note="-0 < 0 is false: usable, 1 - -0 = 1"))
+    ks.append(kat("VE-limit-ulp", anno_of(["0.6500000000000001"] + u[1:]), 0, 84,
+                  note="one ulp above 0.65 fails the strict '>'; term ~7, q = 169 / 2 = 84.5 -> 84"))
+    NW = dict(D)
+    NW["priority"] = [(n, -0.5 if n == "cpu_usage_max_avg_1d" else w) for n, w in D["priority"]]
+    a = anno_of([0.1, 0.1, "1e8", 0.1, 0.1, 0.1], hv=500000000)
+    ks.append(kat("VE-negweight-1e8", a, -1, 85, policy=NW,
+                  note="weights sum to 1.0; term (1 - 1e8) * -0.5 * 100 = +4999999950, the others 90 * 1.5 = 135: "
+                       "q = 5000000085 is past 2^31 and inside int64; - int(5e8 * 10) = 85, inside the clamp"))
+    return ks
+
+
 def make_kats():
     D = pyref.default_policy()
     ks = []
@@ -125,6 +170,7 @@ def make_kats():
     PS["syncPolicy"] = [("cpu_usage_avg_5m", 0)] + D["syncPolicy"][1:]
     ks.append(kat("E-nosync", anno_of([0.99, 0.1, 0.1, 0.1, 0.1, 0.1]), -1, 81, policy=PS,
                   note="period 0: predicate skipped, priority term 0 but weight counted"))
+    ks += value_edge_kats(D)
     # KAT-9: timestamp conversion
     t9 = pyref.go_parse_time("2026-10-15T20:00:00Z", "Asia/Shanghai")
     assert t9 == 1792065600 * 10**9
