@@ -91,6 +91,7 @@ def _load():
         "crane_dyn_refresh_hot_values_async": (C.c_int, [vp, C.c_int64, C.c_int64, vp]),
         "crane_dyn_node_pass_async": (C.c_int, [vp, vp]),
         "crane_dyn_greedy": (C.c_int, [vp, C.c_int64, C.c_int64, vp, vp]),
+        "crane_dyn_greedy_times": (C.c_int, [vp, C.c_int64, vp, vp, vp]),
         "crane_dyn_set_profiling": (C.c_int, [vp, C.c_int]),
         "crane_dyn_stage_times": (C.c_int, [vp, C.c_int32, P(C.c_char_p), P(C.c_double)]),
         "crane_dyn_key_node": (C.c_int64, [C.c_int64, P(C.c_int64)]),
@@ -182,6 +183,7 @@ ABI_SYMBOLS = (
     "crane_dyn_num_predicates", "crane_dyn_filter_counts_async", "crane_dyn_filter_counts",
     "crane_dyn_group_filter_counts",
     "crane_dyn_topk_async", "crane_dyn_topk", "crane_topk_merge", "crane_dyn_group_topk",
+    "crane_dyn_greedy_times",
 )
 
 
@@ -785,6 +787,18 @@ class Engine:
         fl = None if pod_flags is None else np.ascontiguousarray(pod_flags, np.uint8)
         ch = np.empty(n_pods, np.int64)
         self._check(lib.crane_dyn_greedy(self.h, n_pods, int(now_ns), _ptr(fl), _ptr(ch)))
+        return ch
+
+    def greedy_times(self, now_ns, pod_flags=None):
+        """Sequential greedy with pod p scored at now_ns[p] (non-decreasing): chosen[P], global indices."""
+        now = np.ascontiguousarray(now_ns, np.int64)
+        if now.ndim != 1:
+            raise ValueError("now_ns must be one-dimensional")
+        fl = None if pod_flags is None else np.ascontiguousarray(pod_flags, np.uint8)
+        if fl is not None and fl.shape != now.shape:
+            raise ValueError("pod_flags must have one entry per pod")
+        ch = np.empty(len(now), np.int64)
+        self._check(lib.crane_dyn_greedy_times(self.h, len(now), _ptr(now), _ptr(fl), _ptr(ch)))
         return ch
 
 

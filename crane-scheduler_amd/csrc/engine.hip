@@ -256,6 +256,9 @@ struct crane_dyn {
     DevBuf<uint32_t> gcnt;  // greedy: per-window counts [W][N]
     DevBuf<int64_t> gbase, gchosen;
     DevBuf<uint8_t> gleaf, gflags;
+    DevBuf<int64_t> gnow, gunix, gev_off;  // greedy at per-pod times: pod times, the events' CSR by pod
+    DevBuf<unsigned long long> gev_cur;
+    DevBuf<uint32_t> gev;
     DevBuf<unsigned long long> mH, mbs;  // merge-form greedy (merge.hip)
     DevBuf<int32_t> mflag, mapos, mtk;
     DevBuf<int64_t> mFs, mIs, mgi;
@@ -1230,6 +1233,7 @@ int crane_dyn_destroy(crane_dyn* h) {
     h->stage8.release(); h->stagek.release();
     h->k2_sorted.release(); h->hvc.release();
     h->gcnt.release(); h->gbase.release(); h->gchosen.release(); h->gleaf.release(); h->gflags.release();
+    h->gnow.release(); h->gunix.release(); h->gev_off.release(); h->gev_cur.release(); h->gev.release();
     h->mH.release(); h->mbs.release(); h->mflag.release(); h->mapos.release(); h->mtk.release();
     h->mFs.release(); h->mIs.release(); h->mgi.release();
     h->trace.release();
@@ -2477,6 +2481,83 @@ int crane_dyn_greedy(crane_dyn* h, int64_t P, int64_t now_ns, const uint8_t* pod
         HIPTRY(h, launch_greedy(h->shape, h->rec.p, N, h->gcnt.p, a, h->gbase.p, h->gleaf.p, P,
                                 pod_flags ? h->gflags.p : nullptr, h->gchosen.p, st, merge ? kGreedyRun : kGreedyBoth));
     if (P > 0) HIPTRY(h, hipMemcpyAsync(chosen, h->gchosen.p, sizeof(int64_t) * P, hipMemcpyDeviceToHost, st));
+    HIPTRY(h, hipStreamSynchronize(st));
+    for (int64_t p = 0; p < P; ++p)
+        if (chosen[p] >= 0) chosen[p] += h->node_offset;
+    return CRANE_OK;
+}
+
+int crane_dyn_greedy_times(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8_t* pod_flags, int64_t* chosen) {
+    if (!h) return CRANE_E_INVALID;
+    Locked lk(h);
+    if (lk.rc) return lk.rc;
+    if (P < 0 || (P > 0 && (!chosen || !now_ns))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before greedy placement");
+    if (h->N > kGreedyMaxNodes) return h->fail(CRANE_E_INVALID, "greedy mode supports up to 64^4 nodes");
+    for (int64_t p = 1; p < P; ++p)
+        if (now_ns[p] < now_ns[p - 1]) return h->fail(CRANE_E_INVALID, "pod times must not decrease");
+    if (P == 0) return CRANE_OK;
+    HIPTRY(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;
+    hipStream_t st = h->stream;
+    const int64_t N = h->N;
+    if (N == 0) {
+        std::fill(chosen, chosen + P, (int64_t)-1);
+        return CRANE_OK;
+    }
+    // the state at pod 0: crane_dyn_greedy's at now_ns[0] (annotation stamped fresh)
+    const int64_t now0 = now_ns[0];
+    int rc = hot_values_locked(h, now0, now0, st);
+    if (rc) return rc;
+    const int W = h->dp.n_win;
+    HIPTRY(h, h->gcnt.reserve((size_t)std::max(1, W) * (size_t)N));
+    rc = node_pass_locked(h, st, h->gcnt.p);
+    if (rc) return rc;
+    h->rec_dirty = true;  // records now carry the greedy batch's hot values; recompute for eval
+    GreedyTimesArgs ta{};
+    GreedyArgs& a = ta.g;
+    a.now = now0;
+    a.wsum = h->dp.wsum;
+    a.noprio = h->dp.noprio;
+    a.n_win = W;
+    const int64_t unix0 = floor_div(now0, 1000000000LL);
+    for (int w = 0; w < W; ++w) {
+        a.win_count[w] = h->dp.win_count[w];
+        ta.trs[w] = go_seconds_trunc(h->hot_tr[w]);
+        // binding.go:85-91 for Binding{Timestamp: unix_p}, scored at pod p: the same for every p
+        a.win_inc[w] = unix0 > unix0 - ta.trs[w];
+    }
+    HIPTRY(h, h->gbase.reserve((size_t)N));
+    HIPTRY(h, h->gleaf.reserve((size_t)N));
+    HIPTRY(h, h->gchosen.reserve((size_t)P));
+    HIPTRY(h, h->gflags.reserve((size_t)P));
+    HIPTRY(h, h->gnow.reserve((size_t)P));
+    HIPTRY(h, h->gunix.reserve((size_t)P));
+    HIPTRY(h, h->gev_off.reserve((size_t)P + 1));
+    HIPTRY(h, h->gev_cur.reserve((size_t)P));
+    std::vector<int64_t> unixs((size_t)P);
+    for (int64_t p = 0; p < P; ++p) unixs[(size_t)p] = floor_div(now_ns[p], 1000000000LL);
+    HIPTRY(h, hipMemcpyAsync(h->gnow.p, now_ns, sizeof(int64_t) * P, hipMemcpyHostToDevice, st));
+    HIPTRY(h, hipMemcpyAsync(h->gunix.p, unixs.data(), sizeof(int64_t) * P, hipMemcpyHostToDevice, st));
+    if (pod_flags) HIPTRY(h, hipMemcpyAsync(h->gflags.p, pod_flags, P, hipMemcpyHostToDevice, st));
+    HIPTRY(h, launch_greedy(h->shape, h->rec.p, N, h->gcnt.p, a, h->gbase.p, h->gleaf.p, P, nullptr, nullptr, st,
+                            kGreedyPrep));
+    // the events by first pod: count, scan, (the total, for the array) fill
+    HIPTRY(h, hipMemsetAsync(h->gev_cur.p, 0, sizeof(unsigned long long) * P, st));
+    HIPTRY(h, launch_greedy_events(h->shape, h->rec.p, N, h->sd->bnode.p, h->sd->bts.p, h->B, ta, h->gnow.p,
+                                   h->gunix.p, P, h->gev_cur.p, nullptr, 0, false, st));
+    HIPTRY(h, launch_greedy_events_scan(h->gev_cur.p, P, h->gev_off.p, st));
+    int64_t E = 0;
+    HIPTRY(h, hipMemcpyAsync(&E, h->gev_off.p + P, sizeof E, hipMemcpyDeviceToHost, st));
+    HIPTRY(h, hipStreamSynchronize(st));  // (also: unixs is read by its copy until here)
+    HIPTRY(h, h->gev.reserve((size_t)std::max<int64_t>(E, 1)));
+    if (E > 0)
+        HIPTRY(h, launch_greedy_events(h->shape, h->rec.p, N, h->sd->bnode.p, h->sd->bts.p, h->B, ta, h->gnow.p,
+                                       h->gunix.p, P, h->gev_cur.p, h->gev.p, E, true, st));
+    HIPTRY(h, launch_greedy_times(h->shape, h->rec.p, N, h->gcnt.p, ta, h->gbase.p, h->gleaf.p, P, h->gnow.p,
+                                  h->gunix.p, pod_flags ? h->gflags.p : nullptr, h->gchosen.p, h->gev_off.p,
+                                  h->gev.p, st));
+    HIPTRY(h, hipMemcpyAsync(chosen, h->gchosen.p, sizeof(int64_t) * P, hipMemcpyDeviceToHost, st));
     HIPTRY(h, hipStreamSynchronize(st));
     for (int64_t p = 0; p < P; ++p)
         if (chosen[p] >= 0) chosen[p] += h->node_offset;

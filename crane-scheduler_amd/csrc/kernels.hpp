@@ -223,6 +223,29 @@ enum { kGreedyPrep = 1, kGreedyRun = 2, kGreedyBoth = 3 };
 hipError_t launch_greedy(int shape, const void* rec, int64_t N, uint32_t* cnt, const GreedyArgs& a, int64_t* base,
                          uint8_t* leaf, int64_t P, const uint8_t* flags, int64_t* chosen, hipStream_t st,
                          int what = kGreedyBoth);
+// dynamic LDS of the one-workgroup greedy kernels: the tree levels, with the leaves when they fit
+size_t greedy_lds_bytes(int64_t N, bool leaves_in_lds);
+
+// Sequential greedy at per-pod times (greedy_times.hip): pod p scored at now[p], non-decreasing.
+struct GreedyTimesArgs {
+    GreedyArgs g;            // now = now[0]: the state greedy_prep left
+    int64_t trs[kMaxWin];    // int64(timeRange.Seconds()) per window (binding.go:85)
+};
+// The time-driven events between pod 0 and pod P - 1 as a CSR by the first pod that sees them: a
+// node's expiries (record events) and the log bindings leaving a window (bnode / bts: B slots,
+// node outside [0, N) = not counted).  unixs[p] = floor(now[p] / 1e9).  Three launches:
+// fill = false counts the events per pod into cur [P] (zero on entry), the scan turns cur into
+// the groups' starts and writes off [P + 1], fill = true writes ev [E = off[P]] (node | kind << 24).
+hipError_t launch_greedy_events(int shape, const void* rec, int64_t N, const int32_t* bnode, const int64_t* bts,
+                                int64_t B, const GreedyTimesArgs& a, const int64_t* now, const int64_t* unixs,
+                                int64_t P, unsigned long long* cur, uint32_t* ev, int64_t E, bool fill,
+                                hipStream_t st);
+hipError_t launch_greedy_events_scan(unsigned long long* cur, int64_t P, int64_t* off, hipStream_t st);
+// G4: expects greedy_prep's outputs at now[0] (base, leaf, cnt) and the events; chosen [P] local indices
+hipError_t launch_greedy_times(int shape, const void* rec, int64_t N, uint32_t* cnt, const GreedyTimesArgs& a,
+                               int64_t* base, uint8_t* leaf, int64_t P, const int64_t* now, const int64_t* unixs,
+                               const uint8_t* flags, int64_t* chosen, const int64_t* ev_off, const uint32_t* ev,
+                               hipStream_t st);
 
 // Merge form of the sequential greedy (merge.hip)
 struct MergeArgs {

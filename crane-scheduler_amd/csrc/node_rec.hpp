@@ -27,8 +27,9 @@ namespace crane {
 //     |q| < 2^31 beside the full conversion, then base - pen wrapping and the clamp.  Through
 //     score_at it is the score of the per-pair kernel and the answer tables (matrix.hip), the
 //     step path (step.hip, k1stream_body.hpp), topk.hip and select.hip.
-//  3. go_int_g and final_score (greedy.hip): base and penalty of the sequential greedy kernel,
-//     the penalty recomputed from the window counts after every placement.
+//  3. go_int_g and final_score (greedy_dev.hpp): base and penalty of the sequential greedy kernels
+//     (greedy.hip, greedy_times.hip), the penalty recomputed from the window counts after every
+//     placement and, at per-pod times, after every count or expiry that passed.
 //  4. RunIter::next (merge.hip): base - 10 v in plain int64, no wrap — valid because M1 raises
 //     its flag for any base below INT64_MIN + 2^40 (int(NaN), overflow) and crane_dyn_greedy
 //     then runs the sequential kernel instead.

@@ -26,7 +26,7 @@
  * upload_bindings, binding_records, add_bindings, gc_bindings, destroy) and the
  * synchronous calls that run on the engine's own stream (eval, eval_compact,
  * node_steps, node_steps_subset, refresh_hot_values, hot_values, select, greedy,
- * filter_counts, topk)
+ * greedy_times, filter_counts, topk)
  * first wait for the caller streams this engine enqueued asynchronous work on
  * since the last such wait — those streams only, not the device — so they never
  * change a buffer a kernel is still reading.  The engine keeps a caller stream's
@@ -397,6 +397,25 @@ int crane_dyn_stage_times(crane_dyn *h, int32_t max, const char **names, double 
  * chosen node, refreshing its hot value before the next pod is scored.  The
  * hot values start from the uploaded bindings.  chosen[p] as above. */
 int crane_dyn_greedy(crane_dyn *h, int64_t n_pods, int64_t now_ns, const uint8_t *pod_flags, int64_t *chosen);
+
+/* Sequential greedy at per-pod times: pod p is scored at its own now_ns[p]
+ * (non-decreasing), as a scheduler that calls time.Now() per pod does.  For
+ * p = 0 .. n_pods - 1 in order, chosen[p] is what crane_dyn_greedy(h, 1,
+ * now_ns[p], &pod_flags[p], ..) would return on an engine whose binding log is
+ * the uploaded log plus one binding {chosen[q], floor(now_ns[q] / 1e9)} for
+ * every earlier pod q < p with chosen[q] >= 0: hot values at now_ns[p] from
+ * that log with the annotation stamped fresh, crane_dyn_eval's Filter and
+ * Score, the highest score wins and the lowest index among equals, DaemonSet
+ * pods bypass the Filter, -1 = no feasible node; global node indices.  So
+ * between two pods annotations go stale, log bindings leave the hotValue
+ * windows, and the batch's own placements leave them once the batch spans more
+ * than a window.  With all times equal the result is crane_dyn_greedy's.
+ * Synchronous; the engine's binding log is not changed (the caller adds the
+ * bindings it really made).  CRANE_E_INVALID: bad pointers, now_ns decreasing
+ * anywhere, more than 64^4 nodes; CRANE_E_STATE: no nodes uploaded yet;
+ * n_pods = 0 is a no-op. */
+int crane_dyn_greedy_times(crane_dyn *h, int64_t n_pods, const int64_t *now_ns, const uint8_t *pod_flags,
+                           int64_t *chosen);
 
 /* Decode a packed key: returns the global node index (-1 for key < 0) and
  * stores the score in *score (-1 for key < 0) when score != NULL. */
