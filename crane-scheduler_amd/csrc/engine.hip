@@ -1050,28 +1050,51 @@ int flush_pending(crane_dyn* h) {
 }
 }  // namespace
 
+// Records for the kernels that read them: the node pass reruns when they are stale.
+static int records_current(crane_dyn* h, hipStream_t st) { return h->rec_dirty ? node_pass_locked(h, st) : CRANE_OK; }
+
+// What the per-pair kernels read of the engine's state, and K3m's form of it (the node answer
+// tables take it too: now / flags null, P 0).
+static PairIn pair_in(const crane_dyn* h, const int64_t* d_now, const uint8_t* d_flags, int64_t P) {
+    return PairIn{h->rec.p, h->N, h->node_offset, d_now, d_flags, P, h->dp.wsum, h->dp.noprio};
+}
+static MatrixArgs matrix_in(const crane_dyn* h, const int64_t* d_now = nullptr, const uint8_t* d_flags = nullptr,
+                            int64_t P = 0) {
+    MatrixArgs a{pair_in(h, d_now, d_flags, P)};
+    std::memcpy(a.pred_orig, h->pred_orig, sizeof a.pred_orig);
+    return a;
+}
+
+// An entry point's pod arrays: P >= 0 and, with pods, every array it cannot do without.
+static int check_pods(crane_dyn* h, int64_t P, std::initializer_list<const void*> arrays) {
+    bool ok = P >= 0;
+    for (const void* a : arrays) ok = ok && (P == 0 || a);
+    return ok ? CRANE_OK : h->fail(CRANE_E_INVALID, "bad pod arrays");
+}
+
+// The host-pointer forms' staging: the pods go to the engine's device copies, body(d_now, d_flags)
+// enqueues the work and the copies of its results on h->stream, and the stream is waited for.
+template <class Body>
+static int with_host_pods(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8_t* pod_flags, Body body) {
+    HIPTRY(h, h->now.reserve((size_t)P));
+    HIPTRY(h, h->flags.reserve((size_t)P));
+    HIPTRY(h, hipMemcpyAsync(h->now.p, now_ns, sizeof(int64_t) * P, hipMemcpyHostToDevice, h->stream));
+    if (pod_flags) HIPTRY(h, hipMemcpyAsync(h->flags.p, pod_flags, P, hipMemcpyHostToDevice, h->stream));
+    if (int rc = body(h->now.p, pod_flags ? h->flags.p : nullptr)) return rc;
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    return CRANE_OK;
+}
+
 // The per-pair kernel (K3m): first-fail / score matrices [P][ld] and/or keys.
 static int matrix_locked(crane_dyn* h, int64_t P, const int64_t* d_now, const uint8_t* d_flags, long long* d_keys,
                          int8_t* d_ff, void* d_score, bool score_i64, int64_t ld, hipStream_t st) {
-    if (h->rec_dirty) {
-        int rc = node_pass_locked(h, st);
-        if (rc) return rc;
-    }
-    MatrixArgs a{};
-    a.rec = h->rec.p;
-    a.N = h->N;
-    a.node_offset = h->node_offset;
-    a.now = d_now;
-    a.flags = d_flags;
-    a.P = P;
+    if (int rc = records_current(h, st)) return rc;
+    MatrixArgs a = matrix_in(h, d_now, d_flags, P);
     a.ld = ld;
-    a.wsum = h->dp.wsum;
-    a.noprio = h->dp.noprio;
     a.first_fail = d_ff;
     a.score = d_score;
     a.score_i64 = score_i64 ? 1 : 0;
     a.keys = d_keys;
-    std::memcpy(a.pred_orig, h->pred_orig, sizeof a.pred_orig);
     if (d_keys && P > 0) HIPTRY(h, hipMemsetAsync(d_keys, 0xFF, sizeof(long long) * (size_t)P, st));
     HIPTRY(h, launch_matrix(h->shape, a, st));
     return CRANE_OK;
@@ -1549,7 +1572,7 @@ int crane_dyn_eval_keys_async(crane_dyn* h, int64_t P, const int64_t* d_now, con
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && (!d_now || !d_keys))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {d_now, d_keys})) return rc;
     HIPTRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     int rc = keys_locked(h, P, d_now, d_flags, reinterpret_cast<long long*>(d_keys), st);
@@ -1561,7 +1584,7 @@ int crane_dyn_eval_matrix_async(crane_dyn* h, int64_t P, const int64_t* d_now, c
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && !d_now)) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {d_now})) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before evaluating pods");
     if ((d_first_fail || d_score) && ld < h->N) return h->fail(CRANE_E_INVALID, "ld must be >= the node count");
     HIPTRY(h, hipSetDevice(h->device));
@@ -1600,7 +1623,7 @@ int crane_dyn_filter_counts_async(crane_dyn* h, int64_t P, const int64_t* d_now,
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && (!d_now || !d_counts))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {d_now, d_counts})) return rc;
     HIPTRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
     int rc = filter_counts_locked(h, P, d_now, d_flags, d_counts, st);
@@ -1612,22 +1635,18 @@ int crane_dyn_filter_counts(crane_dyn* h, int64_t P, const int64_t* now_ns, cons
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && (!now_ns || !counts))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {now_ns, counts})) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before diagnosing pods");
     if (P == 0) return CRANE_OK;
     HIPTRY(h, hipSetDevice(h->device));
     if (int rc = quiesce(h)) return rc;
     const size_t cells = (size_t)P * (size_t)(h->n_pred_policy + 1);
-    HIPTRY(h, h->now.reserve((size_t)P));
-    HIPTRY(h, h->flags.reserve((size_t)P));
     HIPTRY(h, h->dcounts.reserve(cells));
-    HIPTRY(h, hipMemcpyAsync(h->now.p, now_ns, sizeof(int64_t) * P, hipMemcpyHostToDevice, h->stream));
-    if (pod_flags) HIPTRY(h, hipMemcpyAsync(h->flags.p, pod_flags, P, hipMemcpyHostToDevice, h->stream));
-    if (int rc = filter_counts_locked(h, P, h->now.p, pod_flags ? h->flags.p : nullptr, h->dcounts.p, h->stream))
-        return rc;
-    HIPTRY(h, hipMemcpyAsync(counts, h->dcounts.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, h->stream));
-    HIPTRY(h, hipStreamSynchronize(h->stream));
-    return CRANE_OK;
+    return with_host_pods(h, P, now_ns, pod_flags, [&](const int64_t* d_now, const uint8_t* d_flags) {
+        if (int rc = filter_counts_locked(h, P, d_now, d_flags, h->dcounts.p, h->stream)) return rc;
+        HIPTRY(h, hipMemcpyAsync(counts, h->dcounts.p, sizeof(int32_t) * cells, hipMemcpyDeviceToHost, h->stream));
+        return (int)CRANE_OK;
+    });
 }
 
 // The k best feasible nodes per pod (topk.hip): the records' evaluation of the per-pair kernel,
@@ -1636,23 +1655,12 @@ static int topk_locked(crane_dyn* h, int64_t P, const int64_t* d_now, const uint
                        long long* d_keys, hipStream_t st) {
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before ranking pods' candidates");
     if (P == 0) return CRANE_OK;
-    if (h->rec_dirty) {
-        int rc = node_pass_locked(h, st);
-        if (rc) return rc;
-    }
+    if (int rc = records_current(h, st)) return rc;
     const int64_t S = topk_slices(P, h->N, k, h->opt.topk_slices, h->n_cu);
     if (S < 0)
         return h->fail(CRANE_E_INVALID, "topk_slices leaves node slices of more than 2^24 nodes (or too many workgroups)");
     if (S > 1) HIPTRY(h, h->tkpart.grow((size_t)P * (size_t)S * (size_t)k));
-    TopkArgs a{};
-    a.rec = h->rec.p;
-    a.N = h->N;
-    a.node_offset = h->node_offset;
-    a.now = d_now;
-    a.flags = d_flags;
-    a.P = P;
-    a.wsum = h->dp.wsum;
-    a.noprio = h->dp.noprio;
+    TopkArgs a{pair_in(h, d_now, d_flags, P)};
     a.k = k;
     a.S = (int32_t)S;
     a.out = d_keys;
@@ -1666,7 +1674,7 @@ int crane_dyn_topk_async(crane_dyn* h, int64_t P, const int64_t* d_now, const ui
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && (!d_now || !d_keys))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {d_now, d_keys})) return rc;
     if (k < 1 || k > CRANE_TOPK_MAX) return h->fail(CRANE_E_INVALID, "k must be in [1, CRANE_TOPK_MAX]");
     HIPTRY(h, hipSetDevice(h->device));
     hipStream_t st = stream ? (hipStream_t)stream : h->stream;
@@ -1679,22 +1687,19 @@ int crane_dyn_topk(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8_t
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && (!now_ns || !keys))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {now_ns, keys})) return rc;
     if (k < 1 || k > CRANE_TOPK_MAX) return h->fail(CRANE_E_INVALID, "k must be in [1, CRANE_TOPK_MAX]");
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before ranking pods' candidates");
     if (P == 0) return CRANE_OK;
     HIPTRY(h, hipSetDevice(h->device));
     if (int rc = quiesce(h)) return rc;
     const size_t cells = (size_t)P * (size_t)k;
-    HIPTRY(h, h->now.reserve((size_t)P));
-    HIPTRY(h, h->flags.reserve((size_t)P));
     HIPTRY(h, h->tkeys.reserve(cells));
-    HIPTRY(h, hipMemcpyAsync(h->now.p, now_ns, sizeof(int64_t) * P, hipMemcpyHostToDevice, h->stream));
-    if (pod_flags) HIPTRY(h, hipMemcpyAsync(h->flags.p, pod_flags, P, hipMemcpyHostToDevice, h->stream));
-    if (int rc = topk_locked(h, P, h->now.p, pod_flags ? h->flags.p : nullptr, k, h->tkeys.p, h->stream)) return rc;
-    HIPTRY(h, hipMemcpyAsync(keys, h->tkeys.p, sizeof(long long) * cells, hipMemcpyDeviceToHost, h->stream));
-    HIPTRY(h, hipStreamSynchronize(h->stream));
-    return CRANE_OK;
+    return with_host_pods(h, P, now_ns, pod_flags, [&](const int64_t* d_now, const uint8_t* d_flags) {
+        if (int rc = topk_locked(h, P, d_now, d_flags, k, h->tkeys.p, h->stream)) return rc;
+        HIPTRY(h, hipMemcpyAsync(keys, h->tkeys.p, sizeof(long long) * cells, hipMemcpyDeviceToHost, h->stream));
+        return (int)CRANE_OK;
+    });
 }
 
 // kube-scheduler v1.23.3 numFeasibleNodesToFind (pkg/scheduler/core/generic_scheduler.go,
@@ -1719,7 +1724,7 @@ int crane_dyn_select(crane_dyn* h, int64_t P, const int64_t* d_now, const uint8_
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && (!d_now || !d_chosen))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {d_now, d_chosen})) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before evaluating pods");
     if (dyn_weight < 0 || dyn_weight > (1 << 20)) return h->fail(CRANE_E_INVALID, "dyn_weight must be in [0, 2^20]");
     if (h->N >= (1LL << 32) || h->node_offset + h->N > (1LL << 32))
@@ -1738,19 +1743,8 @@ int crane_dyn_select(crane_dyn* h, int64_t P, const int64_t* d_now, const uint8_
         HIPTRY(h, hipStreamSynchronize(st));
         return CRANE_OK;
     }
-    if (h->rec_dirty) {
-        int rc = node_pass_locked(h, st);
-        if (rc) return rc;
-    }
-    SelArgs a{};
-    a.rec = h->rec.p;
-    a.N = N;
-    a.node_offset = h->node_offset;
-    a.now = d_now;
-    a.flags = d_flags;
-    a.P = P;
-    a.wsum = h->dp.wsum;
-    a.noprio = h->dp.noprio;
+    if (int rc = records_current(h, st)) return rc;
+    SelArgs a{pair_in(h, d_now, d_flags, P)};
     a.ext_ok = d_ext_ok;
     a.ext_score = d_ext_score;
     a.w_dyn = dyn_weight;
@@ -1797,7 +1791,7 @@ int crane_dyn_step_keys_async(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, in
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && (!d_now || !d_keys))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {d_now, d_keys})) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before evaluating pods");
     HIPTRY(h, hipSetDevice(h->device));
     if (!h->busy_q.empty()) {  // (steps on dispatch queues before: they are not ordered with streams)
@@ -1831,7 +1825,7 @@ int crane_dyn_step_keys_queue(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, in
     Locked lk(h, true);  // (a deferred K3s goes into this step's first launch)
     if (lk.rc) return lk.rc;
     if (!q) return h->fail(CRANE_E_INVALID, "null queue");
-    if (P < 0 || (P > 0 && (!d_now || !d_keys))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {d_now, d_keys})) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before evaluating pods");
     HIPTRY(h, hipSetDevice(h->device));
     // a queue is ordered with nothing else: this engine's work on HIP streams or other queues first
@@ -1952,7 +1946,7 @@ int crane_dyn_step_keys_queue(crane_dyn* h, int64_t now_ns, int64_t hv_ts_ns, in
 // at most ~64M entries; chosen nodes come from the same kernel's keys.
 static int eval_host(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8_t* pod_flags, int8_t* first_fail,
                      void* score, bool score_i64, int64_t* chosen, int64_t* chosen_score) {
-    if (P < 0 || (P > 0 && !now_ns)) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {now_ns})) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before evaluating pods");
     HIPTRY(h, hipSetDevice(h->device));
     if (int rc = quiesce(h)) return rc;
@@ -1961,8 +1955,6 @@ static int eval_host(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8
     int64_t pc = P;
     if (matrix && N > 0) pc = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)(64LL << 20) / N));
     if (pc <= 0) pc = 1;
-    HIPTRY(h, h->now.reserve((size_t)pc));
-    HIPTRY(h, h->flags.reserve((size_t)pc));
     HIPTRY(h, h->keys.reserve((size_t)pc));
     HIPTRY(h, h->stagek.reserve((size_t)pc));
     const size_t cells = (size_t)(pc * std::max<int64_t>(N, 1));
@@ -1973,31 +1965,32 @@ static int eval_host(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8
     if (compact && matrix) HIPTRY(h, h->stage8.reserve(2 * cells));
     for (int64_t p0 = 0; p0 < P; p0 += pc) {
         const int64_t np = std::min(pc, P - p0);
-        HIPTRY(h, hipMemcpyAsync(h->now.p, now_ns + p0, sizeof(int64_t) * np, hipMemcpyHostToDevice, h->stream));
-        if (pod_flags)
-            HIPTRY(h, hipMemcpyAsync(h->flags.p, pod_flags + p0, np, hipMemcpyHostToDevice, h->stream));
-        int rc;
-        if (!matrix) {
-            rc = keys_locked(h, np, h->now.p, pod_flags ? h->flags.p : nullptr, h->keys.p, h->stream);
-        } else {
-            void* sdev = !score ? nullptr : score_i64 ? (void*)h->score.p : (void*)h->score8.p;
-            rc = matrix_locked(h, np, h->now.p, pod_flags ? h->flags.p : nullptr, h->keys.p,
-                               first_fail ? h->ff.p : nullptr, sdev, score_i64, N, h->stream);
-        }
-        if (rc) return rc;
-        HIPTRY(h, hipMemcpyAsync(h->stagek.p, h->keys.p, sizeof(long long) * np, hipMemcpyDeviceToHost, h->stream));
         const size_t cnt = (size_t)(np * N);
-        if (first_fail && N > 0)
-            HIPTRY(h, hipMemcpyAsync(compact ? (void*)h->stage8.p : (void*)(first_fail + p0 * N), h->ff.p, cnt,
-                                     hipMemcpyDeviceToHost, h->stream));
-        if (score && N > 0) {
-            if (score_i64)
-                HIPTRY(h, hipMemcpyAsync(static_cast<int64_t*>(score) + p0 * N, h->score.p, sizeof(int64_t) * cnt,
+        const int rc = with_host_pods(h, np, now_ns + p0, pod_flags ? pod_flags + p0 : nullptr,
+                                      [&](const int64_t* d_now, const uint8_t* d_flags) {
+            int rc;
+            if (!matrix) {
+                rc = keys_locked(h, np, d_now, d_flags, h->keys.p, h->stream);
+            } else {
+                void* sdev = !score ? nullptr : score_i64 ? (void*)h->score.p : (void*)h->score8.p;
+                rc = matrix_locked(h, np, d_now, d_flags, h->keys.p, first_fail ? h->ff.p : nullptr, sdev, score_i64, N,
+                                   h->stream);
+            }
+            if (rc) return rc;
+            HIPTRY(h, hipMemcpyAsync(h->stagek.p, h->keys.p, sizeof(long long) * np, hipMemcpyDeviceToHost, h->stream));
+            if (first_fail && N > 0)
+                HIPTRY(h, hipMemcpyAsync(compact ? (void*)h->stage8.p : (void*)(first_fail + p0 * N), h->ff.p, cnt,
                                          hipMemcpyDeviceToHost, h->stream));
-            else
-                HIPTRY(h, hipMemcpyAsync(h->stage8.p + cells, h->score8.p, cnt, hipMemcpyDeviceToHost, h->stream));
-        }
-        HIPTRY(h, hipStreamSynchronize(h->stream));
+            if (score && N > 0) {
+                if (score_i64)
+                    HIPTRY(h, hipMemcpyAsync(static_cast<int64_t*>(score) + p0 * N, h->score.p, sizeof(int64_t) * cnt,
+                                             hipMemcpyDeviceToHost, h->stream));
+                else
+                    HIPTRY(h, hipMemcpyAsync(h->stage8.p + cells, h->score8.p, cnt, hipMemcpyDeviceToHost, h->stream));
+            }
+            return (int)CRANE_OK;
+        });
+        if (rc) return rc;
         if (compact && first_fail && N > 0) std::memcpy(first_fail + p0 * N, h->stage8.p, cnt);
         if (compact && score && N > 0) std::memcpy(static_cast<int8_t*>(score) + p0 * N, h->stage8.p + cells, cnt);
         for (int64_t i = 0; i < np; ++i) {
@@ -2042,21 +2035,12 @@ int crane_dyn_node_steps(crane_dyn* h, int64_t t0_ns, int64_t t1_ns, int64_t n, 
     // a fused step_keys_async on a caller stream may still be writing what the node pass reads
     if (int rc = quiesce(h)) return rc;
     hipStream_t st = h->stream;
-    if (h->rec_dirty) {
-        int rc = node_pass_locked(h, st);
-        if (rc) return rc;
-    }
+    if (int rc = records_current(h, st)) return rc;
     const size_t S = (size_t)node_step_slots(h->shape), N = (size_t)n;
     const size_t o_ns = 8 * N * S, o_ff = o_ns + N, o_sc = o_ff + N * (S + 1), total = o_sc + N * (S + 1);
     HIPTRY(h, h->stp_dev.reserve(total));
     HIPTRY(h, h->stp_host.reserve(total));
-    MatrixArgs a{};
-    a.rec = h->rec.p;
-    a.N = h->N;
-    a.node_offset = h->node_offset;
-    a.wsum = h->dp.wsum;
-    a.noprio = h->dp.noprio;
-    std::memcpy(a.pred_orig, h->pred_orig, sizeof a.pred_orig);
+    const MatrixArgs a = matrix_in(h);
     unsigned char* d = h->stp_dev.p;
     HIPTRY(h, launch_node_steps(h->shape, a, t0_ns, t1_ns, d + o_ns, reinterpret_cast<int64_t*>(d),
                                 reinterpret_cast<int8_t*>(d + o_ff), reinterpret_cast<int8_t*>(d + o_sc), st));
@@ -2165,9 +2149,7 @@ static int update_locked(crane_dyn* h, int64_t k, const int64_t* idx, const doub
     a.hv_ts = h->have_hv ? h->sd->hv_ts.p : nullptr;
     a.rec = h->rec_dirty ? nullptr : h->rec.p;  // current records stay current
     if (rows) {
-        a.ma.wsum = h->dp.wsum;
-        a.ma.noprio = h->dp.noprio;
-        std::memcpy(a.ma.pred_orig, h->pred_orig, sizeof a.ma.pred_orig);
+        a.ma = matrix_in(h);
         a.t0 = rows->t0;
         a.t1 = rows->t1;
         a.bp = reinterpret_cast<int64_t*>(d + o_out);
@@ -2323,10 +2305,7 @@ int crane_dyn_node_steps_subset(crane_dyn* h, int64_t t0_ns, int64_t t1_ns, int6
     HIPTRY(h, hipSetDevice(h->device));
     if (int rc = quiesce(h)) return rc;
     hipStream_t st = h->stream;
-    if (h->rec_dirty) {
-        int rc = node_pass_locked(h, st);
-        if (rc) return rc;
-    }
+    if (int rc = records_current(h, st)) return rc;
     // staging: out bp [k][S] | ns [k] | ff [k][S+1] | sc [k][S+1] | in idx [k]
     const size_t S = (size_t)node_step_slots(h->shape), K = (size_t)k;
     const size_t o_ns = 8 * K * S, o_ff = o_ns + K, o_sc = o_ff + K * (S + 1), o_out = o_sc + K * (S + 1);
@@ -2336,13 +2315,8 @@ int crane_dyn_node_steps_subset(crane_dyn* h, int64_t t0_ns, int64_t t1_ns, int6
     std::memcpy(h->upd_host.p + o_idx, idx, 8 * K);
     unsigned char* d = h->upd_dev.p;
     HIPTRY(h, hipMemcpyAsync(d + o_idx, h->upd_host.p + o_idx, 8 * K, hipMemcpyHostToDevice, st));
-    MatrixArgs a{};
-    a.rec = h->rec.p;
-    a.N = k;
-    a.node_offset = h->node_offset;
-    a.wsum = h->dp.wsum;
-    a.noprio = h->dp.noprio;
-    std::memcpy(a.pred_orig, h->pred_orig, sizeof a.pred_orig);
+    MatrixArgs a = matrix_in(h);
+    a.N = k;  // (rows, not nodes: row j is node idx[j])
     HIPTRY(h, launch_node_steps(h->shape, a, t0_ns, t1_ns, d + o_ns, reinterpret_cast<int64_t*>(d),
                                 reinterpret_cast<int8_t*>(d + o_ff), reinterpret_cast<int8_t*>(d + o_sc), st,
                                 reinterpret_cast<const int64_t*>(d + o_idx)));
@@ -2390,7 +2364,7 @@ int crane_dyn_greedy(crane_dyn* h, int64_t P, int64_t now_ns, const uint8_t* pod
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && !chosen)) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {chosen})) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before greedy placement");
     if (h->N > kGreedyMaxNodes) return h->fail(CRANE_E_INVALID, "greedy mode supports up to 64^4 nodes");
     HIPTRY(h, hipSetDevice(h->device));
@@ -2491,7 +2465,7 @@ int crane_dyn_greedy_times(crane_dyn* h, int64_t P, const int64_t* now_ns, const
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (P < 0 || (P > 0 && (!chosen || !now_ns))) return h->fail(CRANE_E_INVALID, "bad pod arrays");
+    if (int rc = check_pods(h, P, {chosen, now_ns})) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before greedy placement");
     if (h->N > kGreedyMaxNodes) return h->fail(CRANE_E_INVALID, "greedy mode supports up to 64^4 nodes");
     for (int64_t p = 1; p < P; ++p)

@@ -229,11 +229,9 @@ static hipError_t launch_greedy_t(const void* rec, int64_t N, uint32_t* cnt, con
 
 hipError_t launch_greedy(int shape, const void* rec, int64_t N, uint32_t* cnt, const GreedyArgs& a, int64_t* base,
                          uint8_t* leaf, int64_t P, const uint8_t* flags, int64_t* chosen, hipStream_t st, int what) {
-    switch (shape) {
-        case kShape4x6: return launch_greedy_t<4, 6>(rec, N, cnt, a, base, leaf, P, flags, chosen, st, what);
-        case kShape8x8: return launch_greedy_t<8, 8>(rec, N, cnt, a, base, leaf, P, flags, chosen, st, what);
-        default: return launch_greedy_t<16, 16>(rec, N, cnt, a, base, leaf, P, flags, chosen, st, what);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) {
+        return launch_greedy_t<pd(), pr()>(rec, N, cnt, a, base, leaf, P, flags, chosen, st, what);
+    });
 }
 
 }  // namespace crane

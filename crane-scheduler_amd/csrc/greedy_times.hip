@@ -36,6 +36,7 @@
 #include "dyn_types.hpp"
 #include "greedy_dev.hpp"
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace crane {
 
@@ -156,19 +157,6 @@ __device__ __forceinline__ void dec_wg(uint32_t* p) {
 }
 // this wave's vector memory operations so far are done (stores and atomics count in vmcnt)
 __device__ __forceinline__ void vm_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// a value every lane holds (a broadcast LDS read), as a scalar
-__device__ __forceinline__ int64_t uniform64(int64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-__device__ __forceinline__ int64_t readlane64(int64_t v, int l) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 
 // Re-reduce the ancestors of leaf idx (all 64 lanes); stop once an entry is unchanged.
 template <int NLEV>
@@ -340,9 +328,9 @@ __global__ __launch_bounds__(256) void greedy_run_times(const NodeRec<PD, PR>* _
                     int sw = -1;
                     int64_t sh = 0, slim = 0;
                     for (int w = a.n_win - 1; w >= 0; --w) {
-                        if (uniform64(due[w]) <= unixp) {
+                        if (readfirstlane64(due[w]) <= unixp) {
                             sw = w;
-                            sh = uniform64(head[w]);
+                            sh = readfirstlane64(head[w]);
                             slim = unixp - ta.trs[w];
                         }
                     }
@@ -377,7 +365,7 @@ __global__ __launch_bounds__(256) void greedy_run_times(const NodeRec<PD, PR>* _
                     refresh(node, nowp);
                 }
                 next_due = INT64_MAX;
-                for (int w = 0; w < a.n_win; ++w) next_due = min(next_due, uniform64(due[w]));
+                for (int w = 0; w < a.n_win; ++w) next_due = min(next_due, readfirstlane64(due[w]));
                 work = ballot64(in && (ev0 < ev1 || unixv >= next_due));  // (the later pods' bits)
             }
             // ---- 4. descent: root level (<= 64 entries), then one ballot per level
@@ -447,11 +435,9 @@ hipError_t launch_greedy_events(int shape, const void* rec, int64_t N, const int
                                 int64_t P, unsigned long long* cur, uint32_t* ev, int64_t E, bool fill,
                                 hipStream_t st) {
     if (N + B > 0x7FFFFFFFll * kEvThreads) return hipErrorInvalidValue;
-    switch (shape) {
-        case kShape4x6: return launch_events_t<4, 6>(rec, N, bnode, bts, B, a, now, unixs, P, cur, ev, E, fill, st);
-        case kShape8x8: return launch_events_t<8, 8>(rec, N, bnode, bts, B, a, now, unixs, P, cur, ev, E, fill, st);
-        default: return launch_events_t<16, 16>(rec, N, bnode, bts, B, a, now, unixs, P, cur, ev, E, fill, st);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) {
+        return launch_events_t<pd(), pr()>(rec, N, bnode, bts, B, a, now, unixs, P, cur, ev, E, fill, st);
+    });
 }
 
 hipError_t launch_greedy_events_scan(unsigned long long* cur, int64_t P, int64_t* off, hipStream_t st) {
@@ -493,15 +479,9 @@ hipError_t launch_greedy_times(int shape, const void* rec, int64_t N, uint32_t* 
                                const uint8_t* flags, int64_t* chosen, const int64_t* ev_off, const uint32_t* ev,
                                hipStream_t st) {
     if (N <= 0 || N > kGreedyMaxNodes || P <= 0) return hipErrorInvalidValue;
-    switch (shape) {
-        case kShape4x6:
-            return launch_greedy_times_t<4, 6>(rec, N, cnt, a, base, leaf, P, now, unixs, flags, chosen, ev_off, ev, st);
-        case kShape8x8:
-            return launch_greedy_times_t<8, 8>(rec, N, cnt, a, base, leaf, P, now, unixs, flags, chosen, ev_off, ev, st);
-        default:
-            return launch_greedy_times_t<16, 16>(rec, N, cnt, a, base, leaf, P, now, unixs, flags, chosen, ev_off, ev,
-                                                 st);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) {
+        return launch_greedy_times_t<pd(), pr()>(rec, N, cnt, a, base, leaf, P, now, unixs, flags, chosen, ev_off, ev, st);
+    });
 }
 
 }  // namespace crane

@@ -359,19 +359,11 @@ static hipError_t launch_k1_t(const K1Args& a, const K1Step* step, hipStream_t s
 }
 
 hipError_t launch_node_pass(int shape, const K1Args& a, hipStream_t st, const K1Step* step, int stream) {
-    switch (shape) {
-        case kShape4x6: return launch_k1_t<4, 6>(a, step, st, stream);
-        case kShape8x8: return launch_k1_t<8, 8>(a, step, st, stream);
-        default: return launch_k1_t<16, 16>(a, step, st, stream);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) { return launch_k1_t<pd(), pr()>(a, step, st, stream); });
 }
 
 size_t node_rec_bytes(int shape) {
-    switch (shape) {
-        case kShape4x6: return sizeof(NodeRec<4, 6>);
-        case kShape8x8: return sizeof(NodeRec<8, 8>);
-        default: return sizeof(NodeRec<16, 16>);
-    }
+    return with_shape(shape, [](auto pd, auto pr) { return sizeof(NodeRec<pd(), pr()>); });
 }
 
 hipError_t launch_hot_count(const int32_t* bnode, const int64_t* bts, int64_t B, int64_t N, const HotCutoffs& cut,

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <type_traits>
+
 #include "aql.hpp"
 #include "dyn_types.hpp"
 
@@ -11,6 +14,15 @@ namespace crane {
 
 // NodeRec template instances (max predicates x max priorities).
 enum { kShape4x6 = 0, kShape8x8 = 1, kShape16x16 = 2 };
+// f(pd, pr) with the shape's PD and PR as integral constants (template arguments: pd(), pr())
+template <class F>
+inline auto with_shape(int shape, F&& f) {
+    switch (shape) {
+        case kShape4x6: return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 6>{});
+        case kShape8x8: return f(std::integral_constant<int, 8>{}, std::integral_constant<int, 8>{});
+        default: return f(std::integral_constant<int, 16>{}, std::integral_constant<int, 16>{});
+    }
+}
 
 // ---------------------------------------------------------------- launches
 // Kernel timing (crane_dyn_set_profiling): while a KernelTimer is installed on
@@ -80,20 +92,56 @@ struct HotCutoffs {
     int64_t sorted[kMaxWin];
 };
 
+// ---------------------------------------------------------------- per-pair kernels
+// What every kernel that evaluates (pod, node) pairs from the node records reads (K3m, top-k,
+// selection; pair_eval.hpp): the leading part of their arguments, filled in one place.
+struct PairIn {
+    const void* rec;        // NodeRec [N]
+    int64_t N, node_offset;
+    const int64_t* now;     // [P]
+    const uint8_t* flags;   // [P] or null (bit 0: DaemonSet)
+    int64_t P;
+    double wsum;
+    int32_t noprio;
+};
+
+// The grid of K3m and k_sel_pairs: a workgroup per (block of 256 * vec nodes, chunk of pods).
+// About four waves per SIMD (256 CUs x 4 SIMDs = 4096 waves): pods per workgroup from the pair
+// count, multiples of 64 once large, at most max_chunk (the kernel's LDS keys); 8 nodes per lane
+// take four times the pods.  XCD-aware: workgroups are dispatched round-robin over the 8 XCDs, and
+// XCD x (= workgroup id % 8) takes node blocks [x * per, (x + 1) * per) of every chunk, so each
+// XCD's L2 holds 1/8 of the record table.
+constexpr int64_t kPairWaves = 4096;
+struct PairGrid {
+    int32_t chunk, nbx, per, ncy;  // pods per workgroup, node blocks, node blocks per XCD, pod chunks
+    // P, N > 0; false: more workgroups than a grid holds
+    bool make(int64_t P, int64_t N, int vec, int64_t max_chunk) {
+        int64_t c = std::max<int64_t>(1, std::max<int64_t>(1, P * N / kPairWaves) / (64 * vec));
+        if (vec >= 8) c *= 4;
+        if (c >= 64) c = std::min(max_chunk, (c + 63) / 64 * 64);
+        c = std::min(c, P);
+        const int64_t nb = (N + 256 * vec - 1) / (256 * vec), nc = (P + c - 1) / c, pr = (nb + 7) / 8;
+        if (nb > 0x7FFFFFFF / 8 || nc > 0x7FFFFFFF || 8 * pr * nc > 0x7FFFFFFF) return false;
+        chunk = (int32_t)c, nbx = (int32_t)nb, per = (int32_t)pr, ncy = (int32_t)nc;
+        return true;
+    }
+    unsigned workgroups() const { return (unsigned)(8 * (int64_t)per * ncy); }
+    // this workgroup's node block and pod chunk; false (the whole workgroup, so no barrier is
+    // skipped by part of it): past the grid's last
+    __device__ __forceinline__ bool at(int32_t& nb, int32_t& cy) const {
+        const int64_t b = blockIdx.x, q = b >> 3;
+        nb = (int32_t)((b & 7) * per + q % per);
+        cy = (int32_t)(q / per);
+        return nb < nbx && cy < ncy;
+    }
+};
+
 // ---------------------------------------------------------------- K3m (matrix.hip)
 // Per-pair Filter + Score of every (pod, node): first failing predicate and
 // score matrices [P][ld] (row p, column = local node), and/or the per-pod
 // packed keys (max over the shard's feasible nodes).
-struct MatrixArgs {
-    const void* rec;        // NodeRec [N]
-    int64_t N, node_offset;
-    const int64_t* now;     // [P]
-    const uint8_t* flags;   // [P] or null
-    int64_t P;
+struct MatrixArgs : PairIn {
     int64_t ld;             // row stride of the output matrices (>= N)
-    double wsum;
-    int32_t noprio;
-    int32_t pad;
     int8_t* first_fail;     // [P][ld] or null: -1 = Filter Success, else policy predicate index
     void* score;            // [P][ld] int8 or int64 (score_i64), or null
     int32_t score_i64;
@@ -130,17 +178,9 @@ hipError_t launch_filter_counts(const DiagArgs& a, int slices, int n_cu, hipStre
 
 // Top-k candidates (topk.hip, crane_dyn_topk): per pod the k largest keys of the shard's feasible
 // nodes, out[p * k + j] descending ((score << 32) | (0xFFFFFFFF - global node), -1 past the last).
-struct TopkArgs {
-    const void* rec;        // NodeRec [N]
-    int64_t N, node_offset;
-    const int64_t* now;     // [P]
-    const uint8_t* flags;   // [P] or null
-    int64_t P;
-    double wsum;
-    int32_t noprio;
+struct TopkArgs : PairIn {
     int32_t k;              // 1 .. 16
     int32_t S;              // node slices per pod chunk (topk_slices)
-    int32_t pad;
     long long* out;         // [P][k]
     long long* partial;     // [P][S][k] scratch of the slices' rows (S > 1), else null
 };
@@ -182,14 +222,7 @@ hipError_t launch_fill_i64(int64_t* p, int64_t n, int64_t v, hipStream_t st);
 // Framework-level selection (select.hip): upstream kube-scheduler's percentageOfNodesToScore
 // window with a rotating start, the weighted sum of Dynamic's score and the other score
 // plugins' (external), and a lowest-index or seeded tie-break.
-struct SelArgs {
-    const void* rec;           // NodeRec [N]
-    int64_t N, node_offset;
-    const int64_t* now;        // [P]
-    const uint8_t* flags;      // [P] or null (bit 0: DaemonSet)
-    int64_t P;
-    double wsum;
-    int32_t noprio;
+struct SelArgs : PairIn {
     uint32_t kb;               // tie-hash key of the batch (seed != 0)
     const uint8_t* ext_ok;     // [N] or null: 1 = the other filter plugins pass
     const int64_t* ext_score;  // [N] or null: the other score plugins' weighted sum, in [0, 2^30)

@@ -11,16 +11,10 @@
 // time is wave-uniform (v_readlane into SGPRs), so one store instruction writes
 // 64 * VEC consecutive bytes of a matrix row (byte, dword or dwordx2 stores).
 //
-// Why the per-pair work is small and exact: for a node, Filter and Score depend
-// on the pod only through `now < expiry` comparisons (stats.go:42-48), so the
-// node's (first-fail, score) is constant on [lo, hi), the interval between its
-// consecutive expiries around the evaluation time.  A lane keeps its nodes'
-// packed results together with the intersection [LO, HI) of their intervals;
-// a sub-chunk whose pod times [cmin, cmax] lie inside it reuses them (two
-// 64-bit compares per lane).  Otherwise the lane re-reads its node records and
-// re-evaluates at cmin with the literal restatement (score_at, step_node.hpp);
-// a node with one expiry inside (cmin, cmax] also gets its values after that
-// expiry (per pod: compare + select), one with several is evaluated per pod.
+// Why the per-pair work is small and exact: a node's (first-fail, score) is constant between its
+// consecutive expiries, so a lane keeps its nodes' packed results with the intersection [LO, HI)
+// of their intervals and re-reads its records only for a sub-chunk whose pod times leave it (the
+// lane cache of pair_eval.hpp, here in K3m's own lines over the packed bytes of its VEC nodes).
 //
 // Keys: per pod, a lane max of (score << 24 | 0xFFFFFF - local node) over its
 // nodes, a wave max, an LDS max over the workgroup's waves, and one 64-bit
@@ -35,18 +29,13 @@
 #include "kernels.hpp"
 #include "step_node.hpp"
 #include "node_steps.hpp"
+#include "pair_eval.hpp"
 
 namespace crane {
 
 constexpr int kMxT = 256;       // threads per workgroup
 constexpr int kMxChunk = 1024;  // max pods per workgroup (LDS best keys)
 
-
-__device__ __forceinline__ int32_t wave_max32(int32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
-    return v;
-}
 
 __device__ __forceinline__ uint32_t put_byte(uint32_t w, int i, int32_t b) {
     const int sh = 8 * i;
@@ -64,17 +53,14 @@ __device__ __forceinline__ void store_bytes(int8_t* p, const uint32_t* w) {
 }
 
 template <int PD, int PR, int VEC, bool I64, bool OUT, bool KEYS>
-__global__ __launch_bounds__(kMxT) void k3m_matrix(MatrixArgs a, int32_t chunk, int32_t nbx, int32_t per,
-                                                   int32_t ncy) {
+__global__ __launch_bounds__(kMxT) void k3m_matrix(MatrixArgs a, PairGrid g) {
     static_assert(VEC == 1 || VEC == 4 || VEC == 8, "byte, dword or dwordx2 stores");
     static_assert(!I64 || VEC == 1, "int64 scores: one node per lane");
     constexpr int NW = (VEC + 3) / 4;  // packed words per lane
     __shared__ int32_t best[KEYS ? kMxChunk : 1];
-    // XCD-aware: XCD x (= workgroup id % 8) takes node blocks [x*per, (x+1)*per) of every chunk,
-    // so each XCD's L2 holds 1/8 of the record table
-    const int64_t b = blockIdx.x, q = b >> 3;
-    const int32_t nb = (int32_t)((b & 7) * per + q % per), cy = (int32_t)(q / per);
-    if (nb >= nbx || cy >= ncy) return;  // (whole workgroup: no barrier is skipped by part of it)
+    int32_t nb, cy;
+    if (!g.at(nb, cy)) return;
+    const int32_t chunk = g.chunk;
     const int32_t loc0 = threadIdx.x * VEC;  // this lane's first node, local to the workgroup
     const int64_t n0 = (int64_t)nb * (kMxT * VEC) + loc0;
     const int nvalid = (int)max((int64_t)0, min((int64_t)VEC, a.N - n0));  // live nodes of this lane
@@ -85,8 +71,10 @@ __global__ __launch_bounds__(kMxT) void k3m_matrix(MatrixArgs a, int32_t chunk, 
         __syncthreads();
     }
     const NodeRec<PD, PR>* __restrict__ rec = static_cast<const NodeRec<PD, PR>*>(a.rec) + n0;
-    // per lane: results at the last evaluation (f0, s0 packed), valid on [LO, HI); nodes with a step
-    // inside the current sub-chunk: after-step values (f1, s1), the step bp, `multi` = several steps
+    // per lane: the lane cache (pair_eval.hpp) of its VEC nodes, packed and written out here (the
+    // shared form cost this kernel registers): results at the last evaluation (f0, s0), valid on
+    // [LO, HI); nodes with a step inside the current sub-chunk: after-step values (f1, s1), the
+    // step bp, `multi` = several steps
     uint32_t f0w[NW], s0w[NW], f1w[NW], s1w[NW];
     int64_t bp[VEC];
     uint32_t stepped = 0, multi = 0;
@@ -101,12 +89,8 @@ __global__ __launch_bounds__(kMxT) void k3m_matrix(MatrixArgs a, int32_t chunk, 
         const bool pv = lane < nv;
         const int64_t tn = pv ? a.now[q0 + lane] : 0;
         const int32_t fl = pv && a.flags ? (int32_t)(a.flags[q0 + lane] & 1u) : 0;
-        int64_t cmin = pv ? tn : INT64_MAX, cmax = pv ? tn : INT64_MIN;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            cmin = min(cmin, (int64_t)__shfl_xor((long long)cmin, o));
-            cmax = max(cmax, (int64_t)__shfl_xor((long long)cmax, o));
-        }
+        int64_t cmin, cmax;
+        subchunk_range(pv, tn, cmin, cmax);
         if (nvalid > 0 && !(cmin >= LO && cmax < HI)) {
             // re-evaluate this lane's nodes at cmin (rare once the batch's times are covered)
             LO = INT64_MIN;
@@ -142,8 +126,8 @@ __global__ __launch_bounds__(kMxT) void k3m_matrix(MatrixArgs a, int32_t chunk, 
         const bool any_stepped = __ballot(stepped != 0) != 0;
         int32_t kn = -1, kd = -1;  // wave maxima of the flat keys per pod kind
         if (KEYS && !any_stepped) {
-            kn = wave_max32(kn_l);
-            kd = wave_max32(kd_l);
+            kn = wave_max_shfl(kn_l);
+            kd = wave_max_shfl(kd_l);
         }
         for (int j = 0; j < nv; ++j) {
             const bool d = __builtin_amdgcn_readlane(fl, j) != 0;
@@ -201,7 +185,7 @@ __global__ __launch_bounds__(kMxT) void k3m_matrix(MatrixArgs a, int32_t chunk, 
                 }
             }
             if (KEYS) {
-                const int32_t k = any_stepped ? wave_max32(d ? kl_d : kl_n) : (d ? kd : kn);
+                const int32_t k = any_stepped ? wave_max_shfl(d ? kl_d : kl_n) : (d ? kd : kn);
                 if (lane == 0 && k >= 0) atomicMax(&best[q0 + j - p0], k);
             }
         }
@@ -213,92 +197,57 @@ __global__ __launch_bounds__(kMxT) void k3m_matrix(MatrixArgs a, int32_t chunk, 
         for (int i = threadIdx.x; i < (int)(p1 - p0); i += kMxT) {
             const int32_t k = best[i];
             if (k < 0) continue;
-            const int64_t sc = k >> 24;
-            const int64_t g = a.node_offset + (int64_t)nb * (kMxT * VEC) + (0xFFFFFF - (k & 0xFFFFFF));
-            atomicMax(&a.keys[p0 + i], (long long)((sc << 32) | (int64_t)(0xFFFFFFFFull - (uint64_t)g)));
+            atomicMax(&a.keys[p0 + i], wide_key_of(k, a.node_offset + (int64_t)nb * (kMxT * VEC)));
         }
     }
 }
 
-// Launch geometry: VEC nodes per lane and pods per workgroup.  About four waves
-// per SIMD (256 CUs x 4 SIMDs) for small batches (config 2: 5000 x 1000 best at
-// one node per lane, ~19 pods per workgroup: 16.5 us vs 19-24 us for 16 or 64);
-// wide lanes (8 nodes, dwordx2 stores) with 1024-pod workgroups once the batch
-// is large (config 3: 0.47-0.61 ms vs 0.63-0.73 for 16 nodes per lane or 256-pod
-// workgroups; tools/matrix_probe.py).
-struct MatrixGeometry {
-    int vec;
-    int64_t chunk, nbx, ncy, per;
-};
-
-static MatrixGeometry matrix_geometry(const MatrixArgs& a, bool out) {
-    const int64_t pairs = a.P * a.N;
-    const int64_t want_waves = 4096;
-    const int64_t ppw = std::max<int64_t>(1, pairs / want_waves);  // pairs per wave
+// VEC nodes per lane (the pods per workgroup: PairGrid).  One node per lane for small batches
+// (config 2: 5000 x 1000 best at one node per lane, ~19 pods per workgroup: 16.5 us vs 19-24 us
+// for 16 or 64); wide lanes (8 nodes, dwordx2 stores) with 1024-pod workgroups once the batch
+// is large (config 3: 0.47-0.61 ms vs 0.63-0.73 for 16 nodes per lane or 256-pod workgroups).
+static int matrix_vec(const MatrixArgs& a, bool out) {
+    const int64_t ppw = std::max<int64_t>(1, a.P * a.N / kPairWaves);  // pairs per wave
     auto aligned = [&](int v) {
         if (!out) return true;
         if (a.score && a.score_i64) return v == 1;
         const uintptr_t m = (uintptr_t)v - 1;
         return a.ld % v == 0 && ((uintptr_t)a.first_fail & m) == 0 && ((uintptr_t)a.score & m) == 0;
     };
-    MatrixGeometry g{};
-    g.vec = 1;
-    for (int v : {8, 4}) {
-        if (aligned(v) && 64 * v * std::min<int64_t>(a.P, 64) <= ppw) {
-            g.vec = v;
-            break;
-        }
-    }
-    int64_t chunk = std::max<int64_t>(1, ppw / (64 * g.vec));
-    if (g.vec >= 8) chunk *= 4;
-    if (chunk >= 64) chunk = std::min<int64_t>(kMxChunk, (chunk + 63) / 64 * 64);
-    g.chunk = std::min(chunk, a.P);
-    g.nbx = (a.N + kMxT * g.vec - 1) / (kMxT * g.vec);
-    g.ncy = (a.P + g.chunk - 1) / g.chunk;
-    g.per = (g.nbx + 7) / 8;
-    return g;
+    for (int v : {8, 4})
+        if (aligned(v) && 64 * v * std::min<int64_t>(a.P, 64) <= ppw) return v;
+    return 1;
 }
 
 template <int PD, int PR, int VEC>
-static hipError_t launch_vec(const MatrixArgs& a, const MatrixGeometry& g, bool out, bool keys, hipStream_t st) {
-    const int64_t grid = 8 * g.per * g.ncy;
-    if (grid > 0x7FFFFFFF) return hipErrorInvalidValue;
-    const dim3 gr((unsigned)grid), blk(kMxT);
-    const int32_t c32 = (int32_t)g.chunk, nb32 = (int32_t)g.nbx, per32 = (int32_t)g.per, ncy32 = (int32_t)g.ncy;
+static hipError_t launch_vec(const MatrixArgs& a, bool out, bool keys, hipStream_t st) {
+    PairGrid g;
+    if (!g.make(a.P, a.N, VEC, kMxChunk)) return hipErrorInvalidValue;
+    const dim3 gr(g.workgroups()), blk(kMxT);
     const char* nm = out ? (keys ? "k3m_matrix+keys" : "k3m_matrix") : "k3m_keys";
-    if (!out) return klaunch(nm, k3m_matrix<PD, PR, VEC, false, false, true>, gr, blk, 0, st, a, c32, nb32, per32, ncy32);
+    if (!out) return klaunch(nm, k3m_matrix<PD, PR, VEC, false, false, true>, gr, blk, 0, st, a, g);
     if constexpr (VEC == 1) {
         if (a.score && a.score_i64)
-            return keys ? klaunch(nm, k3m_matrix<PD, PR, 1, true, true, true>, gr, blk, 0, st, a, c32, nb32, per32, ncy32)
-                        : klaunch(nm, k3m_matrix<PD, PR, 1, true, true, false>, gr, blk, 0, st, a, c32, nb32, per32,
-                                  ncy32);
+            return keys ? klaunch(nm, k3m_matrix<PD, PR, 1, true, true, true>, gr, blk, 0, st, a, g)
+                        : klaunch(nm, k3m_matrix<PD, PR, 1, true, true, false>, gr, blk, 0, st, a, g);
     }
-    return keys ? klaunch(nm, k3m_matrix<PD, PR, VEC, false, true, true>, gr, blk, 0, st, a, c32, nb32, per32, ncy32)
-                : klaunch(nm, k3m_matrix<PD, PR, VEC, false, true, false>, gr, blk, 0, st, a, c32, nb32, per32, ncy32);
+    return keys ? klaunch(nm, k3m_matrix<PD, PR, VEC, false, true, true>, gr, blk, 0, st, a, g)
+                : klaunch(nm, k3m_matrix<PD, PR, VEC, false, true, false>, gr, blk, 0, st, a, g);
 }
 
-template <int PD, int PR>
-static hipError_t launch_matrix_t(const MatrixArgs& a, hipStream_t st) {
+hipError_t launch_matrix(int shape, const MatrixArgs& a, hipStream_t st) {
     if (a.P <= 0 || a.N <= 0) return hipSuccess;
     const bool out = a.first_fail || a.score;
     const bool keys = a.keys != nullptr;
     if (!out && !keys) return hipSuccess;
     if (out && a.ld < a.N) return hipErrorInvalidValue;
-    const MatrixGeometry g = matrix_geometry(a, out);
-    if (g.nbx > 0x7FFFFFFF / 8 || g.ncy > 0x7FFFFFFF) return hipErrorInvalidValue;
-    switch (g.vec) {
-        case 8: return launch_vec<PD, PR, 8>(a, g, out, keys, st);
-        case 4: return launch_vec<PD, PR, 4>(a, g, out, keys, st);
-        default: return launch_vec<PD, PR, 1>(a, g, out, keys, st);
-    }
-}
-
-hipError_t launch_matrix(int shape, const MatrixArgs& a, hipStream_t st) {
-    switch (shape) {
-        case kShape4x6: return launch_matrix_t<4, 6>(a, st);
-        case kShape8x8: return launch_matrix_t<8, 8>(a, st);
-        default: return launch_matrix_t<16, 16>(a, st);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) {
+        switch (matrix_vec(a, out)) {
+            case 8: return launch_vec<pd(), pr(), 8>(a, out, keys, st);
+            case 4: return launch_vec<pd(), pr(), 4>(a, out, keys, st);
+            default: return launch_vec<pd(), pr(), 1>(a, out, keys, st);
+        }
+    });
 }
 
 // ---------------------------------------------------------------- node answer tables
@@ -319,27 +268,16 @@ __global__ __launch_bounds__(256) void k_node_steps(MatrixArgs a, int64_t t0, in
 }
 
 int node_step_slots(int shape) {
-    switch (shape) {
-        case kShape4x6: return 4 + 6 + 1;
-        case kShape8x8: return 8 + 8 + 1;
-        default: return 16 + 16 + 1;
-    }
+    return with_shape(shape, [](auto pd, auto pr) { return pd() + pr() + 1; });
 }
 
-template <int PD, int PR>
-static hipError_t steps_t(const MatrixArgs& a, int64_t t0, int64_t t1, uint8_t* ns, int64_t* bp, int8_t* ff,
-                          int8_t* sc, const int64_t* idx, hipStream_t st) {
-    return klaunch(idx ? "k_node_steps_subset" : "k_node_steps", k_node_steps<PD, PR>,
-                   dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, a, t0, t1, ns, bp, ff, sc, idx);
-}
 hipError_t launch_node_steps(int shape, const MatrixArgs& a, int64_t t0, int64_t t1, uint8_t* ns, int64_t* bp,
                              int8_t* ff, int8_t* sc, hipStream_t st, const int64_t* idx) {
     if (a.N <= 0) return hipSuccess;
-    switch (shape) {
-        case kShape4x6: return steps_t<4, 6>(a, t0, t1, ns, bp, ff, sc, idx, st);
-        case kShape8x8: return steps_t<8, 8>(a, t0, t1, ns, bp, ff, sc, idx, st);
-        default: return steps_t<16, 16>(a, t0, t1, ns, bp, ff, sc, idx, st);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) {
+        return klaunch(idx ? "k_node_steps_subset" : "k_node_steps", k_node_steps<pd(), pr()>,
+                       dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, a, t0, t1, ns, bp, ff, sc, idx);
+    });
 }
 
 }  // namespace crane

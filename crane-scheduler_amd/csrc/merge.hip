@@ -34,6 +34,7 @@
 
 #include "dyn_types.hpp"
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace crane {
 
@@ -89,10 +90,6 @@ __device__ __forceinline__ RunIter make_iter(const int64_t* base, const uint32_t
     it.cap = cap;
     for (int w = 0; w < kMaxWin; ++w) it.c[w] = w < a.n_win ? cnt[(int64_t)w * N + n] : 0u;
     return it;
-}
-
-__device__ __forceinline__ int64_t pack_level_key(int u, int64_t n) {
-    return ((int64_t)u << 32) | (int64_t)(0xFFFFFFFFull - (uint64_t)n);
 }
 
 // ---------------------------------------------------------------- M1
@@ -249,7 +246,7 @@ __global__ __launch_bounds__(kMT) void m4_place(const int64_t* __restrict__ base
             unsigned long long p0 = off[(int64_t)(100 - u) * gridDim.x + blockIdx.x] + x - c;
             for (int i = 0; i < w; ++i) p0 += wc[i][u];
             const unsigned long long p1 = min(p0 + c, (unsigned long long)cap);
-            for (unsigned long long p = p0; p < p1; ++p) stream[p] = pack_level_key(u, n);
+            for (unsigned long long p = p0; p < p1; ++p) stream[p] = wide_key(u, n);
         }
     }
 }

@@ -35,6 +35,7 @@
 #include "dyn_types.hpp"
 #include "kernels.hpp"
 #include "step_node.hpp"
+#include "pair_eval.hpp"
 
 namespace crane {
 
@@ -363,11 +364,7 @@ __global__ __launch_bounds__(kRsT) void k_sel_chain_rs(SelArgs a, const int64_t*
         lo = min(lo, t);
         hi = max(hi, t);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        lo = min(lo, (int64_t)__shfl_xor((long long)lo, o));
-        hi = max(hi, (int64_t)__shfl_xor((long long)hi, o));
-    }
+    wave_minmax64(lo, hi);
     if (lane == 0) {
         red[0][wv] = lo;
         red[1][wv] = hi;
@@ -691,19 +688,18 @@ __global__ __launch_bounds__(kRsT) void k_sel_chain_rs(SelArgs a, const int64_t*
 constexpr int kSelT = 256;       // threads (one node each)
 constexpr int kSelChunk = 1024;  // max pods per workgroup (LDS keys)
 
-__device__ __forceinline__ long long wave_max64(long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = max(v, (long long)__shfl_xor(v, o));
-    return v;
-}
+// the cached value: the Filter passes (non-DaemonSet pods) and the score
+struct SelVal {
+    bool f;
+    int32_t s;
+};
 
 template <int PD, int PR>
-__global__ __launch_bounds__(kSelT) void k_sel_pairs(SelArgs a, int32_t chunk, int32_t nbx, int32_t per,
-                                                     int32_t ncy) {
+__global__ __launch_bounds__(kSelT) void k_sel_pairs(SelArgs a, PairGrid g) {
     __shared__ unsigned long long best[kSelChunk];
-    const int64_t b = blockIdx.x, q = b >> 3;  // XCD x (= workgroup id % 8) takes node blocks [x*per, (x+1)*per)
-    const int32_t nb = (int32_t)((b & 7) * per + q % per), cy = (int32_t)(q / per);
-    if (nb >= nbx || cy >= ncy) return;  // (whole workgroup)
+    int32_t nb, cy;
+    if (!g.at(nb, cy)) return;
+    const int32_t chunk = g.chunk;
     const int64_t n = (int64_t)nb * kSelT + threadIdx.x;
     const bool valid = n < a.N;
     const int64_t p0 = (int64_t)cy * chunk, p1 = min(a.P, p0 + chunk);
@@ -714,11 +710,10 @@ __global__ __launch_bounds__(kSelT) void k_sel_pairs(SelArgs a, int32_t chunk, i
     const int64_t ext = valid && a.ext_score ? a.ext_score[n] : 0;
     const bool ok = valid && (!a.ext_ok || a.ext_ok[n] != 0);
     const uint32_t tb = tie_node(a.seed, a.kb, (uint32_t)(a.node_offset + n));
-    // lane cache (K3m): Filter pass (non-DaemonSet) and score at the last evaluation, valid
-    // on [LO, HI); a step inside the sub-chunk: values from bp on; multi: evaluate per pod
-    bool f0 = false, f1 = false, stepped = false, multi = false;
-    int32_t s0 = 0, s1 = 0;
-    int64_t bp = INT64_MAX, LO = INT64_MAX, HI = INT64_MIN;
+    const auto eval = [&](int64_t t, const NodeRec<PD, PR>& r) {
+        return SelVal{!(t < r.e_fail), score_at<PD, PR>(t, r, a.wsum, a.noprio)};
+    };
+    PairCache<SelVal> c;  // this lane's node (pair_eval.hpp); stays empty without one
     for (int64_t q0 = p0; q0 < p1; q0 += 64) {
         const int nv = (int)min((int64_t)64, p1 - q0);
         const bool pv = lane < nv;
@@ -727,30 +722,11 @@ __global__ __launch_bounds__(kSelT) void k_sel_pairs(SelArgs a, int32_t chunk, i
         const int64_t ws = pv && a.wstart ? a.wstart[q0 + lane] : 0;
         const int64_t wl = pv && a.wstart ? a.wlen[q0 + lane] : a.N;
         const uint32_t cp = pv ? tie_pod_key(a.seed, q0 + lane) : 0u;
-        int64_t cmin = pv ? tn : INT64_MAX, cmax = pv ? tn : INT64_MIN;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            cmin = min(cmin, (int64_t)__shfl_xor((long long)cmin, o));
-            cmax = max(cmax, (int64_t)__shfl_xor((long long)cmax, o));
-        }
-        if (ok && !(cmin >= LO && cmax < HI)) {
+        int64_t cmin, cmax;
+        subchunk_range(pv, tn, cmin, cmax);
+        if (ok && !c.covers(cmin, cmax)) {
             const NodeRec<PD, PR> r = *rec;
-            int64_t lo, hi;
-            bracket<PD, PR>(r, cmin, lo, hi);
-            f0 = !(cmin < r.e_fail);
-            s0 = score_at<PD, PR>(cmin, r, a.wsum, a.noprio);
-            LO = lo;
-            HI = hi;
-            stepped = hi <= cmax;
-            multi = false;
-            if (stepped) {
-                int64_t lo2, hi2;
-                bracket<PD, PR>(r, hi, lo2, hi2);
-                bp = hi;
-                f1 = !(hi < r.e_fail);
-                s1 = score_at<PD, PR>(hi, r, a.wsum, a.noprio);
-                multi = hi2 <= cmax;
-            }
+            c.refresh(r, cmin, cmax, eval);
         }
         // the pods whose window meets this workgroup's node block (a few % of them with
         // adaptive windows): the block's first node inside the window, or the window's first
@@ -763,23 +739,15 @@ __global__ __launch_bounds__(kSelT) void k_sel_pairs(SelArgs a, int32_t chunk, i
             if (r2 < 0) r2 += a.N;
             pm = __ballot(pv && (r1 < wl || r2 < kSelT));
         }
+        const bool stepped = c.bp != INT64_MAX;  // (in this sub-chunk or, reused, an earlier one)
         while (pm) {
             const int j = __ffsll((long long)pm) - 1;
             pm &= pm - 1;
             const int64_t t = readlane64(tn, j);
             const bool d = __builtin_amdgcn_readlane(fl, j) != 0;
-            bool f = f0;
-            int32_t s = s0;
-            if (ok && stepped) {
-                if (multi) {
-                    const NodeRec<PD, PR> r = *rec;
-                    f = !(t < r.e_fail);
-                    s = score_at<PD, PR>(t, r, a.wsum, a.noprio);
-                } else if (t >= bp) {
-                    f = f1;
-                    s = s1;
-                }
-            }
+            const SelVal x = stepped ? c.at(t, rec, eval) : c.v0;
+            const bool f = x.f;
+            const int32_t s = x.s;
             bool in = true;
             if (a.wstart) {  // rotated position of this node in the pod's window
                 int64_t rel = n - readlane64(ws, j);
@@ -818,17 +786,11 @@ __global__ __launch_bounds__(256) void k_sel_decode(SelArgs a, int64_t* __restri
 }
 
 // ---------------------------------------------------------------- launchers
-template <int PD, int PR>
-static hipError_t fth_t(const SelArgs& a, int64_t* fth, hipStream_t st) {
-    return klaunch("k_sel_fth", k_sel_fth<PD, PR>, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, a, fth);
-}
 hipError_t launch_select_fth(const SelArgs& a, int shape, int64_t* fth, hipStream_t st) {
     if (a.N <= 0) return hipSuccess;
-    switch (shape) {
-        case kShape4x6: return fth_t<4, 6>(a, fth, st);
-        case kShape8x8: return fth_t<8, 8>(a, fth, st);
-        default: return fth_t<16, 16>(a, fth, st);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) {
+        return klaunch("k_sel_fth", k_sel_fth<pd(), pr()>, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, st, a, fth);
+    });
 }
 
 hipError_t launch_select_chain(const SelArgs& a, const int64_t* fth, int64_t K, int64_t start, int64_t* wstart,
@@ -850,26 +812,13 @@ hipError_t launch_select_chain(const SelArgs& a, const int64_t* fth, int64_t K, 
                    next_start, rs ? (const int32_t*)done : nullptr);
 }
 
-template <int PD, int PR>
-static hipError_t pairs_t(const SelArgs& a, hipStream_t st) {
-    const int64_t nbx = (a.N + kSelT - 1) / kSelT;
-    // about 4096 waves: pods per workgroup from the pair count (multiples of 64 once large)
-    const int64_t ppw = std::max<int64_t>(1, a.P * a.N / 4096);
-    int64_t chunk = std::max<int64_t>(1, ppw / 64);
-    if (chunk >= 64) chunk = std::min<int64_t>(kSelChunk, (chunk + 63) / 64 * 64);
-    chunk = std::min(chunk, a.P);
-    const int64_t ncy = (a.P + chunk - 1) / chunk, per = (nbx + 7) / 8;
-    if (8 * per * ncy > 0x7FFFFFFF) return hipErrorInvalidValue;
-    return klaunch("k_sel_pairs", k_sel_pairs<PD, PR>, dim3((unsigned)(8 * per * ncy)), dim3(kSelT), 0, st, a,
-                   (int32_t)chunk, (int32_t)nbx, (int32_t)per, (int32_t)ncy);
-}
 hipError_t launch_select_pairs(int shape, const SelArgs& a, hipStream_t st) {
     if (a.P <= 0 || a.N <= 0) return hipSuccess;
-    switch (shape) {
-        case kShape4x6: return pairs_t<4, 6>(a, st);
-        case kShape8x8: return pairs_t<8, 8>(a, st);
-        default: return pairs_t<16, 16>(a, st);
-    }
+    PairGrid g;
+    if (!g.make(a.P, a.N, 1, kSelChunk)) return hipErrorInvalidValue;
+    return with_shape(shape, [&](auto pd, auto pr) {
+        return klaunch("k_sel_pairs", k_sel_pairs<pd(), pr()>, dim3(g.workgroups()), dim3(kSelT), 0, st, a, g);
+    });
 }
 
 hipError_t launch_select_decode(const SelArgs& a, int64_t* chosen, int64_t* total, hipStream_t st) {

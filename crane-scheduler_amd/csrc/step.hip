@@ -542,10 +542,7 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
             }
             const bool live = grp * kK3sPods + u * TH + threadIdx.x < P;
             if (live && best >= 0) {
-                const int64_t sc = best >> 24;
-                const int64_t n = 0xFFFFFF - (best & 0xFFFFFF);
-                atomicMax(&keys[praw[u] & 0x7FFFFFFF],
-                          (long long)((sc << 32) | (int64_t)(0xFFFFFFFFull - (uint64_t)(node_offset + n))));
+                atomicMax(&keys[praw[u] & 0x7FFFFFFF], wide_key_of(best, node_offset));
             }
         }
         if (h + 1 < kPPL / kV) asm volatile("" ::: "memory");  // (the next pass's loads stay behind this one's)
@@ -555,11 +552,7 @@ __device__ __forceinline__ void k3s_body(const int64_t b, const StepTables& st, 
 
 // ---------------------------------------------------------------- launchers
 int step_breakpoints(int shape) {
-    switch (shape) {
-        case kShape4x6: return 6 + 2;
-        case kShape8x8: return 8 + 2;
-        default: return 16 + 2;
-    }
+    return with_shape(shape, [](auto, auto pr) { return pr() + 2; });
 }
 
 __global__ __launch_bounds__(kK3sThreads) void k3s_eval(StepTables st, const int32_t* __restrict__ perm,
@@ -734,11 +727,9 @@ hipError_t launch_step_nodes(int shape, const void* rec, int64_t N, double wsum,
                              const StepTables& st, const StepGeometry& g, const int64_t* tile_mm, hipStream_t s) {
     if (N <= 0 || g.ntiles <= 0) return hipSuccess;
     if (N >= kStepMaxNodes) return hipErrorInvalidValue;
-    switch (shape) {
-        case kShape4x6: return launch_steps_t<4, 6>(rec, N, wsum, noprio, st, g, tile_mm, s);
-        case kShape8x8: return launch_steps_t<8, 8>(rec, N, wsum, noprio, st, g, tile_mm, s);
-        default: return launch_steps_t<16, 16>(rec, N, wsum, noprio, st, g, tile_mm, s);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) {
+        return launch_steps_t<pd(), pr()>(rec, N, wsum, noprio, st, g, tile_mm, s);
+    });
 }
 
 hipError_t launch_k3s_delta_pods(const K3sBatch& b, const int32_t* bnode, int64_t N, const HotDelta& d, uint32_t* adj,

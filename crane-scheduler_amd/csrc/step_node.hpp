@@ -16,6 +16,7 @@
 
 #include "dyn_types.hpp"
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace crane {
 
@@ -26,47 +27,6 @@ __device__ __forceinline__ int64_t xcd_block(int64_t b, int64_t nb) {
     const int64_t x = b & 7, q = b >> 3, per = nb >> 3, rem = nb & 7;
     return x * per + (x < rem ? x : rem) + q;
 }
-
-__device__ __forceinline__ int32_t pack_key(int32_t f, int64_t n) { return (f << 24) | (int32_t)(0xFFFFFF - n); }
-
-// ---- wave primitives on DPP (VALU lane moves, no LDS round trip like ds_bpermute's
-// __shfl*).  Every lane of the 64-lane wave must be active (uniform control flow).
-// dpp_ctrl: quad_perm 0x00-0xFF, row_shr:k 0x110 + k, row_ror:k 0x120 + k, row_bcast:15 0x142,
-// row_bcast:31 0x143; lanes whose source is outside the row keep `id` (bound_ctrl off).
-template <int CTRL, int ROWS = 0xF>
-__device__ __forceinline__ int32_t dpp_or(int32_t id, int32_t v) {
-    return __builtin_amdgcn_update_dpp(id, v, CTRL, ROWS, 0xF, false);
-}
-// maximum over the wave, uniform
-__device__ __forceinline__ int32_t wave_max(int32_t v) {
-    v = max(v, dpp_or<0xB1>(v, v));   // quad_perm [1,0,3,2]
-    v = max(v, dpp_or<0x4E>(v, v));   // quad_perm [2,3,0,1]
-    v = max(v, dpp_or<0x124>(v, v));  // row_ror:4
-    v = max(v, dpp_or<0x128>(v, v));  // row_ror:8: every lane holds its row's maximum
-    return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-               max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
-// inclusive prefix (lane order) under an associative op with identity id: Hillis-Steele
-// within each row of 16, then rows 1 / 3 take row 0 / 2's total, rows 2-3 rows 0-1's
-template <class Op>
-__device__ __forceinline__ int32_t wave_scan(int32_t v, int32_t id, Op op) {
-    v = op(v, dpp_or<0x111>(id, v));
-    v = op(v, dpp_or<0x112>(id, v));
-    v = op(v, dpp_or<0x114>(id, v));
-    v = op(v, dpp_or<0x118>(id, v));
-    v = op(v, dpp_or<0x142, 0xA>(id, v));
-    v = op(v, dpp_or<0x143, 0xC>(id, v));
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_scan_add(uint32_t v) {
-    return (uint32_t)wave_scan((int32_t)v, 0, [](int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); });
-}
-__device__ __forceinline__ int32_t wave_scan_max(int32_t v) {
-    return wave_scan(v, INT32_MIN, [](int32_t a, int32_t b) { return max(a, b); });
-}
-// lane i takes lane (i ^ 1)'s value / lane i + 2's within its quad (lanes 0, 1 of a quad)
-__device__ __forceinline__ int32_t quad_xor1(int32_t v) { return dpp_or<0xB1>(v, v); }
-__device__ __forceinline__ int32_t quad_down2(int32_t v) { return dpp_or<0xEE>(v, v); }
 
 // Exact clamped Score of (pod at time t, node) — the literal int64 restatement
 // of stats.go:114-138 + plugins.go:91-93, the semantics of K3's eval_pair and
@@ -127,11 +87,7 @@ __device__ __forceinline__ void batch_range_load(const int64_t* __restrict__ til
 template <int BS>
 __device__ __forceinline__ void batch_range_reduce(int64_t mn, int64_t mx, int64_t* smn, int64_t* smx, int64_t& tmin,
                                                    int64_t& tmax) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        mn = min(mn, (int64_t)__shfl_xor((long long)mn, o));
-        mx = max(mx, (int64_t)__shfl_xor((long long)mx, o));
-    }
+    wave_minmax64(mn, mx);
     if ((threadIdx.x & 63) == 0) {
         smn[threadIdx.x >> 6] = mn;
         smx[threadIdx.x >> 6] = mx;
@@ -182,18 +138,6 @@ __device__ __forceinline__ uint32_t wg_excl_scan_u32(uint32_t v, uint32_t* part)
     for (int i = 0; i < BT / 64; ++i) pre += i < w ? part[i] : 0u;
     __syncthreads();
     return pre + x - v;
-}
-
-// a 64-bit value of lane j / of the first active lane, uniform
-__device__ __forceinline__ int64_t readlane64(int64_t v, int j) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), j);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ int64_t readfirstlane64(int64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 // Per node and pod kind: the flat key (-1 if stepped or never feasible) and,

@@ -3,13 +3,10 @@
 // crane_dyn_eval_keys_async), best first, -1 where the pod has fewer feasible nodes — the
 // runner-up candidates of a pod without the P x N matrices (matrix.hip) they could be ranked from.
 //
-// Evaluation is the per-pair kernel's (K3m, matrix.hip), with the same literal restatement
-// (step_node.hpp: bracket, score_at and the Filter of key_of, now < e_fail; no score or filter
-// arithmetic is restated here): a lane owns one node of a 256-node block, evaluates it at the
-// minimum time of a 64-pod sub-chunk and keeps the two keys (per pod kind) with the interval
-// [LO, HI) between the node's expiries on which they hold.  A sub-chunk inside the interval reuses
-// them; a node with one expiry inside the sub-chunk also holds its keys after it (per pod: compare
-// + select); one with several is evaluated per pod.
+// Evaluation is the per-pair kernels' lane cache (pair_eval.hpp) with the two keys of a node (per pod
+// kind) as its value, from the same literal restatement (step_node.hpp: score_at and the Filter of
+// key_of, now < e_fail; no score or filter arithmetic is restated here): a lane owns one node of a
+// 256-node block and evaluates it at the minimum time of a 64-pod sub-chunk.
 //
 // Phase 1 (k_topk): a workgroup takes a chunk of CH pods and a slice of whole node blocks.  Every
 // (wave, pod) has a sorted list of KC keys in LDS (KC = 4, 8, 16: the smallest >= k), stored
@@ -44,6 +41,7 @@
 #include "dyn_types.hpp"
 #include "kernels.hpp"
 #include "step_node.hpp"
+#include "pair_eval.hpp"
 
 namespace crane {
 
@@ -55,6 +53,21 @@ constexpr int64_t kTkSliceMax = (int64_t)1 << 24;  // nodes per slice (pack_key'
 // anything, and writes k partial keys per pod for the second phase to read
 constexpr int kTkWgPerCu = 2;
 constexpr int kTkMinBlk = 8;
+
+// the cached value: a node's list keys for the pods the Filter applies to (kn) and DaemonSet pods (kd)
+struct TkKeys {
+    int32_t kn = -1, kd = -1;  // (-1: not a candidate — a lane without a node)
+};
+template <int PD, int PR>
+struct TkEval {
+    double wsum;
+    int32_t noprio;
+    int64_t loc;  // the node's index within the slice
+    __device__ __forceinline__ TkKeys operator()(int64_t t, const NodeRec<PD, PR>& r) const {
+        const int32_t sc = score_at<PD, PR>(t, r, wsum, noprio);
+        return {key_of<PD, PR>(0, t, sc, r, loc), key_of<PD, PR>(1, t, sc, r, loc)};
+    }
+};
 
 template <int PD, int PR, int KC>
 __global__ __launch_bounds__(kTkT) void k_topk(TopkArgs a) {
@@ -80,12 +93,8 @@ __global__ __launch_bounds__(kTkT) void k_topk(TopkArgs a) {
     for (int q = w; q < nsc; q += 4) {  // the sub-chunks' time ranges
         const int i = q * 64 + lane;
         const int64_t tn = i < nlive ? a.now[p0 + i] : 0;
-        int64_t mn = i < nlive ? tn : INT64_MAX, mx = i < nlive ? tn : INT64_MIN;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            mn = min(mn, (int64_t)__shfl_xor((long long)mn, o));
-            mx = max(mx, (int64_t)__shfl_xor((long long)mx, o));
-        }
+        int64_t mn, mx;
+        subchunk_range(i < nlive, tn, mn, mx);
         if (lane == 0) {
             scmin[q] = mn;
             scmax[q] = mx;
@@ -105,34 +114,16 @@ __global__ __launch_bounds__(kTkT) void k_topk(TopkArgs a) {
         const bool valid = n < a.N;
         const int64_t locb = (nb - b0) * kTkT + loc0;  // the wave's first node within the slice
         const int64_t loc = locb + lane;
-        // lane = node: its keys per pod kind at the last evaluation (kn: the Filter applies, kd:
-        // DaemonSet), valid on [LO, HI); a node with a step inside the sub-chunk: the keys from bp
-        // on, `multi` = several steps
-        int32_t kn0 = -1, kd0 = -1, kn1 = -1, kd1 = -1;
-        int64_t bp = INT64_MAX, LO = INT64_MAX, HI = INT64_MIN;  // empty: evaluate at the first sub-chunk
-        int32_t multi = 0;
+        // lane = node: its keys per pod kind, cached over the sub-chunks
+        PairCache<TkKeys> c;
         for (int q = 0; q < nsc; ++q) {
             const int nv = min(64, nlive - q * 64);
             const int64_t cmin = scmin[q], cmax = scmax[q];
-            if (valid && !(cmin >= LO && cmax < HI)) {
+            if (valid && !c.covers(cmin, cmax)) {
                 const NodeRec<PD, PR> r = rec[n];
-                bracket<PD, PR>(r, cmin, LO, HI);
-                const int32_t sc = score_at<PD, PR>(cmin, r, a.wsum, a.noprio);
-                kn0 = key_of<PD, PR>(0, cmin, sc, r, loc);
-                kd0 = key_of<PD, PR>(1, cmin, sc, r, loc);
-                bp = INT64_MAX;
-                multi = 0;
-                if (HI <= cmax) {  // a step inside the sub-chunk: the keys from HI on
-                    bp = HI;
-                    int64_t lo2, hi2;
-                    bracket<PD, PR>(r, bp, lo2, hi2);
-                    const int32_t s1 = score_at<PD, PR>(bp, r, a.wsum, a.noprio);
-                    kn1 = key_of<PD, PR>(0, bp, s1, r, loc);
-                    kd1 = key_of<PD, PR>(1, bp, s1, r, loc);
-                    multi = hi2 <= cmax ? 1 : 0;
-                }
+                c.refresh(r, cmin, cmax, TkEval<PD, PR>{a.wsum, a.noprio, loc});
             }
-            const bool stepped = bp <= cmax;  // (reused keys of an earlier sub-chunk's stepped node: bp = HI > cmax)
+            const bool stepped = c.bp <= cmax;  // (reused keys of an earlier sub-chunk's stepped node: bp = hi > cmax)
             uint64_t smask = __ballot(stepped);
 
             // lane = pod from here: its time, kind, threshold and (once an offer is taken) its list
@@ -164,7 +155,7 @@ __global__ __launch_bounds__(kTkT) void k_topk(TopkArgs a) {
 
             // the nodes without a step: their keys hold for every pod of a kind, so they are offered
             // best first (wave maximum, then the next) until no pod of the kind takes one
-            int32_t rn = stepped ? -1 : kn0, rd = stepped ? -1 : kd0;
+            int32_t rn = stepped ? -1 : c.v0.kn, rd = stepped ? -1 : c.v0.kd;
             if (__ballot(live && !ds) != 0) {
                 for (;;) {
                     const int32_t c = wave_max(rn);
@@ -184,18 +175,13 @@ __global__ __launch_bounds__(kTkT) void k_topk(TopkArgs a) {
             while (smask) {
                 const int j = __builtin_ctzll(smask);
                 smask &= smask - 1;
-                int32_t kn, kd;
-                if (__builtin_amdgcn_readlane(multi, j)) {
-                    const NodeRec<PD, PR> r = rec[nb * kTkT + w * 64 + j];
-                    const int32_t sc = score_at<PD, PR>(tn, r, a.wsum, a.noprio);
-                    kn = key_of<PD, PR>(0, tn, sc, r, locb + j);
-                    kd = key_of<PD, PR>(1, tn, sc, r, locb + j);
-                } else {
-                    const bool after = tn >= readlane64(bp, j);
-                    kn = after ? __builtin_amdgcn_readlane(kn1, j) : __builtin_amdgcn_readlane(kn0, j);
-                    kd = after ? __builtin_amdgcn_readlane(kd1, j) : __builtin_amdgcn_readlane(kd0, j);
-                }
-                offer(ds ? kd : kn);
+                PairCache<TkKeys> b;  // node j's, uniform
+                b.multi = __builtin_amdgcn_readlane((int)c.multi, j) != 0;
+                b.bp = readlane64(c.bp, j);
+                b.v0 = {__builtin_amdgcn_readlane(c.v0.kn, j), __builtin_amdgcn_readlane(c.v0.kd, j)};
+                b.v1 = {__builtin_amdgcn_readlane(c.v1.kn, j), __builtin_amdgcn_readlane(c.v1.kd, j)};
+                const TkKeys x = b.at(tn, rec + nb * kTkT + w * 64 + j, TkEval<PD, PR>{a.wsum, a.noprio, locb + j});
+                offer(ds ? x.kd : x.kn);
             }
             if (have) {
 #pragma unroll
@@ -225,8 +211,7 @@ __global__ __launch_bounds__(kTkT) void k_topk(TopkArgs a) {
                 else if (v1 == m) ++h1;
                 else if (v2 == m) ++h2;
                 else ++h3;
-                const int64_t g = g0 + (0xFFFFFF - (m & 0xFFFFFF));
-                key = (long long)(((int64_t)(m >> 24) << 32) | (int64_t)(0xFFFFFFFFull - (uint64_t)g));
+                key = wide_key_of(m, g0);
             }
             o[x] = key;
         }
@@ -250,8 +235,7 @@ __global__ __launch_bounds__(kTkT) void k_topk_merge(const long long* __restrict
                 const long long v = row[e];
                 if (v < prev) m = max(m, v);
             }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
+            m = wave_max64(m);
         }
         if (lane == 0) out[p * k + x] = m;
         prev = m;
@@ -275,24 +259,16 @@ int64_t topk_slices(int64_t P, int64_t N, int k, int slices, int n_cu) {
     return S;
 }
 
-template <int PD, int PR>
-static hipError_t launch_topk_t(const TopkArgs& a, hipStream_t st) {
-    const dim3 g((unsigned)((a.P + topk_chunk(a.k) - 1) / topk_chunk(a.k) * a.S)), b(kTkT);
-    if (a.k <= 4) return klaunch("k_topk", k_topk<PD, PR, 4>, g, b, 0, st, a);
-    if (a.k <= 8) return klaunch("k_topk", k_topk<PD, PR, 8>, g, b, 0, st, a);
-    return klaunch("k_topk", k_topk<PD, PR, 16>, g, b, 0, st, a);
-}
-
 hipError_t launch_topk(int shape, const TopkArgs& a, hipStream_t st) {
     if (a.P <= 0) return hipSuccess;
     if (a.k < 1 || a.k > 16 || a.S < 1 || (a.S > 1 && !a.partial)) return hipErrorInvalidValue;
     if (a.N <= 0) return hipMemsetAsync(a.out, 0xFF, sizeof(long long) * (size_t)a.P * (size_t)a.k, st);
-    hipError_t e;
-    switch (shape) {
-        case kShape4x6: e = launch_topk_t<4, 6>(a, st); break;
-        case kShape8x8: e = launch_topk_t<8, 8>(a, st); break;
-        default: e = launch_topk_t<16, 16>(a, st); break;
-    }
+    const dim3 g((unsigned)((a.P + topk_chunk(a.k) - 1) / topk_chunk(a.k) * a.S)), b(kTkT);
+    const hipError_t e = with_shape(shape, [&](auto pd, auto pr) {
+        if (a.k <= 4) return klaunch("k_topk", k_topk<pd(), pr(), 4>, g, b, 0, st, a);
+        if (a.k <= 8) return klaunch("k_topk", k_topk<pd(), pr(), 8>, g, b, 0, st, a);
+        return klaunch("k_topk", k_topk<pd(), pr(), 16>, g, b, 0, st, a);
+    });
     if (e != hipSuccess || a.S == 1) return e;
     return klaunch("k_topk_merge", k_topk_merge, dim3((unsigned)((a.P + kTkT / 64 - 1) / (kTkT / 64))), dim3(kTkT), 0, st,
                    (const long long*)a.partial, a.P, a.S, a.k, a.out);

@@ -71,11 +71,9 @@ __global__ __launch_bounds__(256) void k_fill_i64(int64_t* p, int64_t n, int64_t
 hipError_t launch_update_nodes(int shape, const UpdateArgs& a, hipStream_t st) {
     if (a.k <= 0) return hipSuccess;
     const dim3 g((unsigned)((a.k + 255) / 256)), b(256);
-    switch (shape) {
-        case kShape4x6: return klaunch("k_update_nodes", k_update_nodes<4, 6>, g, b, 0, st, a);
-        case kShape8x8: return klaunch("k_update_nodes", k_update_nodes<8, 8>, g, b, 0, st, a);
-        default: return klaunch("k_update_nodes", k_update_nodes<16, 16>, g, b, 0, st, a);
-    }
+    return with_shape(shape, [&](auto pd, auto pr) {
+        return klaunch("k_update_nodes", k_update_nodes<pd(), pr()>, g, b, 0, st, a);
+    });
 }
 
 hipError_t launch_fill_i64(int64_t* p, int64_t n, int64_t v, hipStream_t st) {
