@@ -2360,41 +2360,69 @@ int crane_dyn_stage_times(crane_dyn* h, int32_t max, const char** names, double*
     return n;
 }
 
-int crane_dyn_greedy(crane_dyn* h, int64_t P, int64_t now_ns, const uint8_t* pod_flags, int64_t* chosen) {
-    if (!h) return CRANE_E_INVALID;
-    Locked lk(h);
-    if (lk.rc) return lk.rc;
-    if (int rc = check_pods(h, P, {chosen})) return rc;
+// ---- sequential greedy: what crane_dyn_greedy and crane_dyn_greedy_times share
+static int greedy_check(crane_dyn* h, int64_t P, std::initializer_list<const void*> arrays) {
+    if (int rc = check_pods(h, P, arrays)) return rc;
     if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before greedy placement");
     if (h->N > kGreedyMaxNodes) return h->fail(CRANE_E_INVALID, "greedy mode supports up to 64^4 nodes");
-    HIPTRY(h, hipSetDevice(h->device));
-    if (int rc = quiesce(h)) return rc;
+    return CRANE_OK;
+}
+
+// The state before the first pod, at now0 (the engine quiesced): hot values from the binding log
+// with the annotation stamped now0 (fresh), K1's records with the per-window counts in gcnt, the
+// kernels' arguments (ta.g, and int64(timeRange.Seconds()) per window in ta.trs), the per-node
+// and per-pod buffers, and the pods' flags on the device.
+static int greedy_begin(crane_dyn* h, int64_t P, int64_t now0, const uint8_t* pod_flags, GreedyTimesArgs& ta) {
     hipStream_t st = h->stream;
     const int64_t N = h->N;
-    // hot values from the binding log at `now`, annotation stamped `now` (fresh)
-    int rc = hot_values_locked(h, now_ns, now_ns, st);
-    if (rc) return rc;
+    if (int rc = hot_values_locked(h, now0, now0, st)) return rc;
     const int W = h->dp.n_win;
     HIPTRY(h, h->gcnt.reserve((size_t)std::max(1, W) * (size_t)std::max<int64_t>(N, 1)));
-    rc = node_pass_locked(h, st, h->gcnt.p);
-    if (rc) return rc;
+    if (int rc = node_pass_locked(h, st, h->gcnt.p)) return rc;
     h->rec_dirty = true;  // records now carry the greedy batch's hot values; recompute for eval
-    GreedyArgs a{};
-    a.now = now_ns;
+    ta = GreedyTimesArgs{};
+    GreedyArgs& a = ta.g;
+    a.now = now0;
     a.wsum = h->dp.wsum;
     a.noprio = h->dp.noprio;
     a.n_win = W;
-    const int64_t now_unix = floor_div(now_ns, 1000000000LL);
+    const int64_t unix0 = floor_div(now0, 1000000000LL);
     for (int w = 0; w < W; ++w) {
         a.win_count[w] = h->dp.win_count[w];
-        // binding.go:85-91 for Binding{Timestamp: now_unix}
-        a.win_inc[w] = now_unix > now_unix - go_seconds_trunc(h->hot_tr[w]);
+        ta.trs[w] = go_seconds_trunc(h->hot_tr[w]);
+        // binding.go:85-91 for Binding{Timestamp: unix_p}, scored at pod p: the same for every p
+        a.win_inc[w] = unix0 > unix0 - ta.trs[w];
     }
     HIPTRY(h, h->gbase.reserve((size_t)std::max<int64_t>(N, 1)));
     HIPTRY(h, h->gleaf.reserve((size_t)std::max<int64_t>(N, 1)));
     HIPTRY(h, h->gchosen.reserve((size_t)std::max<int64_t>(P, 1)));
     HIPTRY(h, h->gflags.reserve((size_t)std::max<int64_t>(P, 1)));
     if (pod_flags && P > 0) HIPTRY(h, hipMemcpyAsync(h->gflags.p, pod_flags, P, hipMemcpyHostToDevice, st));
+    return CRANE_OK;
+}
+
+// gchosen to the host, local node indices to global ones
+static int greedy_end(crane_dyn* h, int64_t P, int64_t* chosen) {
+    if (P > 0) HIPTRY(h, hipMemcpyAsync(chosen, h->gchosen.p, sizeof(int64_t) * P, hipMemcpyDeviceToHost, h->stream));
+    HIPTRY(h, hipStreamSynchronize(h->stream));
+    for (int64_t p = 0; p < P; ++p)
+        if (chosen[p] >= 0) chosen[p] += h->node_offset;
+    return CRANE_OK;
+}
+
+int crane_dyn_greedy(crane_dyn* h, int64_t P, int64_t now_ns, const uint8_t* pod_flags, int64_t* chosen) {
+    if (!h) return CRANE_E_INVALID;
+    Locked lk(h);
+    if (lk.rc) return lk.rc;
+    if (int rc = greedy_check(h, P, {chosen})) return rc;
+    HIPTRY(h, hipSetDevice(h->device));
+    if (int rc = quiesce(h)) return rc;
+    hipStream_t st = h->stream;
+    const int64_t N = h->N;
+    GreedyTimesArgs ta;
+    if (int rc = greedy_begin(h, P, now_ns, pod_flags, ta)) return rc;
+    const GreedyArgs& a = ta.g;
+    const int W = a.n_win;
     // Merge form (merge.hip) when every hotValue count is positive; else the sequential kernel
     bool merge = h->opt.greedy_form == 0 && N > 0 && P > 0;
     for (int w = 0; w < W; ++w) merge = merge && a.win_count[w] > 0;
@@ -2405,12 +2433,7 @@ int crane_dyn_greedy(crane_dyn* h, int64_t P, int64_t now_ns, const uint8_t* pod
             for (int64_t p = 0; p < P; ++p) Pd += pod_flags[p] & 1;
         HIPTRY(h, launch_greedy(h->shape, h->rec.p, N, h->gcnt.p, a, h->gbase.p, h->gleaf.p, P, nullptr, nullptr, st,
                                 kGreedyPrep));
-        MergeArgs ma{};
-        ma.n_win = W;
-        for (int w = 0; w < W; ++w) {
-            ma.win_count[w] = a.win_count[w];
-            ma.win_inc[w] = a.win_inc[w];
-        }
+        const MergeArgs ma = merge_args(a);
         HIPTRY(h, h->mH.reserve(2 * 101));
         HIPTRY(h, h->mflag.reserve(1));
         HIPTRY(h, launch_merge_hist(h->gbase.p, h->gleaf.p, h->gcnt.p, N, ma, P, Pd, h->mH.p, h->mflag.p, st));
@@ -2454,20 +2477,14 @@ int crane_dyn_greedy(crane_dyn* h, int64_t P, int64_t now_ns, const uint8_t* pod
     if (!done)
         HIPTRY(h, launch_greedy(h->shape, h->rec.p, N, h->gcnt.p, a, h->gbase.p, h->gleaf.p, P,
                                 pod_flags ? h->gflags.p : nullptr, h->gchosen.p, st, merge ? kGreedyRun : kGreedyBoth));
-    if (P > 0) HIPTRY(h, hipMemcpyAsync(chosen, h->gchosen.p, sizeof(int64_t) * P, hipMemcpyDeviceToHost, st));
-    HIPTRY(h, hipStreamSynchronize(st));
-    for (int64_t p = 0; p < P; ++p)
-        if (chosen[p] >= 0) chosen[p] += h->node_offset;
-    return CRANE_OK;
+    return greedy_end(h, P, chosen);
 }
 
 int crane_dyn_greedy_times(crane_dyn* h, int64_t P, const int64_t* now_ns, const uint8_t* pod_flags, int64_t* chosen) {
     if (!h) return CRANE_E_INVALID;
     Locked lk(h);
     if (lk.rc) return lk.rc;
-    if (int rc = check_pods(h, P, {chosen, now_ns})) return rc;
-    if (h->N < 0) return h->fail(CRANE_E_STATE, "upload nodes before greedy placement");
-    if (h->N > kGreedyMaxNodes) return h->fail(CRANE_E_INVALID, "greedy mode supports up to 64^4 nodes");
+    if (int rc = greedy_check(h, P, {chosen, now_ns})) return rc;
     for (int64_t p = 1; p < P; ++p)
         if (now_ns[p] < now_ns[p - 1]) return h->fail(CRANE_E_INVALID, "pod times must not decrease");
     if (P == 0) return CRANE_OK;
@@ -2479,32 +2496,10 @@ int crane_dyn_greedy_times(crane_dyn* h, int64_t P, const int64_t* now_ns, const
         std::fill(chosen, chosen + P, (int64_t)-1);
         return CRANE_OK;
     }
-    // the state at pod 0: crane_dyn_greedy's at now_ns[0] (annotation stamped fresh)
-    const int64_t now0 = now_ns[0];
-    int rc = hot_values_locked(h, now0, now0, st);
-    if (rc) return rc;
-    const int W = h->dp.n_win;
-    HIPTRY(h, h->gcnt.reserve((size_t)std::max(1, W) * (size_t)N));
-    rc = node_pass_locked(h, st, h->gcnt.p);
-    if (rc) return rc;
-    h->rec_dirty = true;  // records now carry the greedy batch's hot values; recompute for eval
-    GreedyTimesArgs ta{};
-    GreedyArgs& a = ta.g;
-    a.now = now0;
-    a.wsum = h->dp.wsum;
-    a.noprio = h->dp.noprio;
-    a.n_win = W;
-    const int64_t unix0 = floor_div(now0, 1000000000LL);
-    for (int w = 0; w < W; ++w) {
-        a.win_count[w] = h->dp.win_count[w];
-        ta.trs[w] = go_seconds_trunc(h->hot_tr[w]);
-        // binding.go:85-91 for Binding{Timestamp: unix_p}, scored at pod p: the same for every p
-        a.win_inc[w] = unix0 > unix0 - ta.trs[w];
-    }
-    HIPTRY(h, h->gbase.reserve((size_t)N));
-    HIPTRY(h, h->gleaf.reserve((size_t)N));
-    HIPTRY(h, h->gchosen.reserve((size_t)P));
-    HIPTRY(h, h->gflags.reserve((size_t)P));
+    // the state at pod 0: crane_dyn_greedy's at now_ns[0]
+    GreedyTimesArgs ta;
+    if (int rc = greedy_begin(h, P, now_ns[0], pod_flags, ta)) return rc;
+    const GreedyArgs& a = ta.g;
     HIPTRY(h, h->gnow.reserve((size_t)P));
     HIPTRY(h, h->gunix.reserve((size_t)P));
     HIPTRY(h, h->gev_off.reserve((size_t)P + 1));
@@ -2513,7 +2508,6 @@ int crane_dyn_greedy_times(crane_dyn* h, int64_t P, const int64_t* now_ns, const
     for (int64_t p = 0; p < P; ++p) unixs[(size_t)p] = floor_div(now_ns[p], 1000000000LL);
     HIPTRY(h, hipMemcpyAsync(h->gnow.p, now_ns, sizeof(int64_t) * P, hipMemcpyHostToDevice, st));
     HIPTRY(h, hipMemcpyAsync(h->gunix.p, unixs.data(), sizeof(int64_t) * P, hipMemcpyHostToDevice, st));
-    if (pod_flags) HIPTRY(h, hipMemcpyAsync(h->gflags.p, pod_flags, P, hipMemcpyHostToDevice, st));
     HIPTRY(h, launch_greedy(h->shape, h->rec.p, N, h->gcnt.p, a, h->gbase.p, h->gleaf.p, P, nullptr, nullptr, st,
                             kGreedyPrep));
     // the events by first pod: count, scan, (the total, for the array) fill
@@ -2531,11 +2525,7 @@ int crane_dyn_greedy_times(crane_dyn* h, int64_t P, const int64_t* now_ns, const
     HIPTRY(h, launch_greedy_times(h->shape, h->rec.p, N, h->gcnt.p, ta, h->gbase.p, h->gleaf.p, P, h->gnow.p,
                                   h->gunix.p, pod_flags ? h->gflags.p : nullptr, h->gchosen.p, h->gev_off.p,
                                   h->gev.p, st));
-    HIPTRY(h, hipMemcpyAsync(chosen, h->gchosen.p, sizeof(int64_t) * P, hipMemcpyDeviceToHost, st));
-    HIPTRY(h, hipStreamSynchronize(st));
-    for (int64_t p = 0; p < P; ++p)
-        if (chosen[p] >= 0) chosen[p] += h->node_offset;
-    return CRANE_OK;
+    return greedy_end(h, P, chosen);
 }
 
 }  // extern "C"

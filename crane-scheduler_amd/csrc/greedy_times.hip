@@ -16,11 +16,13 @@
 //    binary search over the pod times.  The order inside a pod's group is whatever the fill's
 //    atomic cursors gave and nothing depends on it: decrements commute and a touched node's
 //    leaf is recomputed from its final counts.
-// G4 greedy_run_times: greedy_run's one workgroup, tree and descent; before each descent wave 0
-//    advances the window heads, applies the pod's event group 64 events per round and, for every
-//    node touched, recomputes base (greedy_base, as greedy_prep), feasibility and the leaf at
-//    now[p] and re-reduces its ancestors.  A node not touched keeps a base computed at an
-//    earlier time, valid because none of its expiries lies in between.
+// G4 greedy_run_times: one workgroup over greedy_dev.hpp's tree, descent and re-reduction,
+//    the code greedy_run calls, with the counts and base[] reached through WgAccess; before each
+//    descent wave 0 advances the window heads, applies the pod's event group 64 events per round
+//    and, for every node touched, recomputes base (greedy_base, as greedy_prep), feasibility and
+//    the leaf at now[p] and re-reduces its ancestors.  A node not touched keeps a base computed
+//    at an earlier time, valid because none of its expiries lies in between.  chosen[p] is
+//    stored per pod: a later pod's window head reads it.
 //
 // The counts are decremented with atomics (two lanes of a round can hit one node).  The kernel is
 // one workgroup, so workgroup scope is the whole of it: its atomics, and its other accesses to
@@ -139,52 +141,12 @@ __global__ __launch_bounds__(kScanThreads) void ev_scan(unsigned long long* __re
     if (threadIdx.x == kScanThreads - 1) off[P] = (int64_t)part[kScanThreads - 1];
 }
 
-// ---- workgroup-scope accesses to what this workgroup also changes with atomics
-__device__ __forceinline__ uint32_t ld_wg(const uint32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ int64_t ld_wg(const int64_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void st_wg(uint32_t* p, uint32_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void st_wg(int64_t* p, int64_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
+// ---- the workgroup-scope accesses beside WgAccess's loads and stores (greedy_dev.hpp)
 __device__ __forceinline__ void dec_wg(uint32_t* p) {
     (void)__hip_atomic_fetch_sub(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 // this wave's vector memory operations so far are done (stores and atomics count in vmcnt)
 __device__ __forceinline__ void vm_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// Re-reduce the ancestors of leaf idx (all 64 lanes); stop once an entry is unchanged.
-template <int NLEV>
-__device__ __forceinline__ void tree_rereduce(const Tree& t, const uint8_t* leaf, int64_t idx, int lane) {
-    int64_t child = idx;
-#pragma unroll
-    for (int l = 1; l <= NLEV; ++l) {
-        const int64_t e = child / 64, c = e * 64 + lane;
-        int va = -1, vf = -1;
-        if (c < t.size[l - 1]) {
-            if (l == 1) {
-                va = leaf_val(leaf[c], true);
-                vf = leaf_val(leaf[c], false);
-            } else {
-                va = ent_val(t.lvl[l - 1][c], true);
-                vf = ent_val(t.lvl[l - 1][c], false);
-            }
-        }
-        const int ma = wave_max_dpp(va), mf = wave_max_dpp(vf);
-        const uint16_t ne = (uint16_t)(max(ma, 0) | ((mf + 1) << 8));
-        const uint16_t oe = t.lvl[l][e];
-        if (ne == oe) break;
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) t.lvl[l][e] = ne;
-        __builtin_amdgcn_wave_barrier();
-        child = e;
-    }
-}
 
 template <int PD, int PR, int NLEV>
 __global__ __launch_bounds__(256) void greedy_run_times(const NodeRec<PD, PR>* __restrict__ rec, int64_t N,
@@ -198,60 +160,11 @@ __global__ __launch_bounds__(256) void greedy_run_times(const NodeRec<PD, PR>* _
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const GreedyArgs& a = ta.g;
-    // layout and build as greedy_run: [leaves (if in LDS)] [level 1] [level 2] ...; every index into
-    // t.size / t.lvl is a compile-time constant (the level loops are fully unrolled)
     Tree t;
-    t.size[0] = N;
-    t.nlev = NLEV;
-    int64_t state_off;
-    {
-        int64_t off = leaves_in_lds ? (N + 15) / 16 * 16 : 0, sz = N;
-#pragma unroll
-        for (int l = 1; l <= NLEV; ++l) {
-            sz = (sz + 63) / 64;
-            t.size[l] = sz;
-            t.lvl[l] = reinterpret_cast<uint16_t*>(smem + off);
-            off += (sz * 2 + 15) / 16 * 16;
-        }
-        state_off = off;
-    }
+    const int64_t state_off = tree_layout<NLEV>(t, smem, N, leaves_in_lds);
     uint8_t* leaf = leaves_in_lds ? smem : leaf_g;
-    if (leaves_in_lds)
-        for (int64_t i = threadIdx.x; i < N; i += blockDim.x) leaf[i] = leaf_g[i];
-    // warm this XCD's L2 with the per-node state the commits touch (as greedy_run)
-    {
-        uint64_t x = 0;
-        for (int64_t i = threadIdx.x; i < N; i += blockDim.x) {
-            x ^= (uint64_t)ld_wg(&base[i]);
-            for (int w = 0; w < a.n_win; ++w) x ^= ld_wg(&cnt[(int64_t)w * N + i]);
-        }
-        if (x == 0x9E3779B97F4A7C15ull && P < 0) chosen[0] = (int64_t)x;  // never true: keeps the loads
-    }
-    __syncthreads();
-#pragma unroll
-    for (int l = 1; l <= NLEV; ++l) {
-        for (int64_t e = threadIdx.x; e < t.size[l]; e += blockDim.x) {
-            int ma = 0, mf = -1;
-            for (int j = 0; j < 64; ++j) {
-                const int64_t c = e * 64 + j;
-                if (c >= t.size[l - 1]) break;
-                int va, vf;
-                if (l == 1) {
-                    va = leaf_val(leaf[c], true);
-                    vf = leaf_val(leaf[c], false);
-                } else {
-                    va = ent_val(t.lvl[l - 1][c], true);
-                    vf = ent_val(t.lvl[l - 1][c], false);
-                }
-                ma = max(ma, va);
-                mf = max(mf, vf);
-            }
-            t.lvl[l][e] = (uint16_t)(ma | ((mf + 1) << 8));
-        }
-        __syncthreads();
-    }
+    tree_load_build<NLEV, WgAccess>(t, leaf, leaf_g, N, base, cnt, a.n_win, P, chosen);
     if (wave != 0) return;
-    constexpr int top = NLEV;
 
     // The lanes' nodes (node < 0: none) had a count or an expiry pass: base, feasibility and leaf
     // at nowp from the record and the counts as they are now, then the ancestors of every leaf
@@ -266,11 +179,11 @@ __global__ __launch_bounds__(256) void greedy_run_times(const NodeRec<PD, PR>* _
 #pragma unroll
             for (int w = 0; w < kMaxWin; ++w) {
                 if (w >= a.n_win) break;
-                v += win_quot(ld_wg(&cnt[(int64_t)w * N + node]), a.win_count[w]);
+                v += win_quot(WgAccess::ld(&cnt[(int64_t)w * N + node]), a.win_count[w]);
             }
             const uint8_t nl = greedy_leaf(b, pen_of_sum(v), feasible);
             changed = nl != leaf[node];
-            st_wg(&base[node], b);  // (the commit reads it)
+            WgAccess::st(&base[node], b);  // (the commit reads it)
             leaf[node] = nl;
         }
         vm_done();
@@ -340,7 +253,7 @@ __global__ __launch_bounds__(256) void greedy_run_times(const NodeRec<PD, PR>* _
                         const int64_t h = sh + lane;
                         const bool out = h < p && unixs[h] <= slim;  // a prefix of the lanes: times never decrease
                         if (out) {
-                            node = (int32_t)ld_wg(&chosen[h]);
+                            node = (int32_t)WgAccess::ld(&chosen[h]);
                             if (node >= 0) dec_wg(&cnt[(int64_t)sw * N + node]);
                         }
                         const int64_t nh = sh + __builtin_popcountll(ballot64(out));  // in (sh, p]
@@ -368,44 +281,30 @@ __global__ __launch_bounds__(256) void greedy_run_times(const NodeRec<PD, PR>* _
                 for (int w = 0; w < a.n_win; ++w) next_due = min(next_due, readfirstlane64(due[w]));
                 work = ballot64(in && (ev0 < ev1 || unixv >= next_due));  // (the later pods' bits)
             }
-            // ---- 4. descent: root level (<= 64 entries), then one ballot per level
-            const bool any = (dsmask >> q) & 1;
-            const int v = lane < t.size[top] ? ent_val(t.lvl[top][lane], any) : -1;
-            const int M = wave_max_dpp(v);
-            int64_t idx = -1;
-            if (M >= 0) {
-                idx = __builtin_ctzll(ballot64(v == M));
-#pragma unroll
-                for (int l = top - 1; l >= 0; --l) {
-                    const int64_t c = idx * 64 + lane;
-                    int w = -1;
-                    if (c < t.size[l]) w = l == 0 ? leaf_val(leaf[c], any) : ent_val(t.lvl[l][c], any);
-                    idx = idx * 64 + __builtin_ctzll(ballot64(w == M));
-                }
-            }
+            // ---- 4. descent, then the commit: Binding{Node: idx, Timestamp: unix_p}
+            const int64_t idx = tree_descend<NLEV>(t, leaf, (dsmask >> q) & 1, lane);
             if (idx < 0) {
-                if (lane == 0) st_wg(&chosen[p], idx);
+                if (lane == 0) WgAccess::st(&chosen[p], idx);
                 continue;
             }
-            // ---- commit: Binding{Node: idx, Timestamp: unix_p}
             if (lane == 0) {
                 // one round trip: counts and base load together, counts stored back
                 uint32_t c[kMaxWin];
 #pragma unroll
                 for (int w = 0; w < kMaxWin; ++w)
-                    if (w < a.n_win) c[w] = ld_wg(&cnt[(int64_t)w * N + idx]);
-                const int64_t b = ld_wg(&base[idx]);
+                    if (w < a.n_win) c[w] = WgAccess::ld(&cnt[(int64_t)w * N + idx]);
+                const int64_t b = WgAccess::ld(&base[idx]);
                 int64_t v = 0;
 #pragma unroll
                 for (int w = 0; w < kMaxWin; ++w) {
                     if (w >= a.n_win) break;
                     c[w] += a.win_inc[w] ? 1u : 0u;
-                    st_wg(&cnt[(int64_t)w * N + idx], c[w]);
+                    WgAccess::st(&cnt[(int64_t)w * N + idx], c[w]);
                     v += win_quot(c[w], a.win_count[w]);
                 }
                 const uint8_t old = leaf[idx];
                 leaf[idx] = (uint8_t)(final_score(b, pen_of_sum(v)) | (old & 0x80));
-                st_wg(&chosen[p], idx);  // (a later pod's step 1 reads it)
+                WgAccess::st(&chosen[p], idx);  // (a later pod's step 1 reads it)
             }
             // LDS instructions of one wave execute in order; a global leaf store is waited for
             if (!leaves_in_lds) vm_done();
@@ -444,43 +343,18 @@ hipError_t launch_greedy_events_scan(unsigned long long* cur, int64_t P, int64_t
     return klaunch("greedy_ev_scan", ev_scan, dim3(1), dim3(kScanThreads), 0, st, cur, P, off);
 }
 
-template <int PD, int PR>
-static hipError_t launch_greedy_times_t(const void* rec, int64_t N, uint32_t* cnt, const GreedyTimesArgs& a,
-                                        int64_t* base, uint8_t* leaf, int64_t P, const int64_t* now,
-                                        const int64_t* unixs, const uint8_t* flags, int64_t* chosen,
-                                        const int64_t* ev_off, const uint32_t* ev, hipStream_t st) {
-    const bool in_lds = greedy_lds_bytes(N, true) + kGreedyTimesState <= kGreedyLdsBytes;
-    const size_t lds = greedy_lds_bytes(N, in_lds) + kGreedyTimesState;
-    int nlev = 0;
-    for (int64_t sz = N; nlev == 0 || sz > 64;) {
-        sz = (sz + 63) / 64;
-        ++nlev;
-    }
-    const NodeRec<PD, PR>* r = static_cast<const NodeRec<PD, PR>*>(rec);
-#define GREEDY_TIMES_LAUNCH(L)                                                                                     \
-    do {                                                                                                           \
-        static const hipError_t attr = hipFuncSetAttribute((const void*)greedy_run_times<PD, PR, L>,               \
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        if (attr != hipSuccess) return attr;                                                                       \
-        return klaunch("greedy_run_times", greedy_run_times<PD, PR, L>, dim3(1), dim3(256), lds, st, r, N, leaf,   \
-                       base, cnt, a, P, now, unixs, flags, chosen, ev_off, ev, (int32_t)in_lds);                   \
-    } while (0)
-    switch (nlev) {
-        case 1: GREEDY_TIMES_LAUNCH(1);
-        case 2: GREEDY_TIMES_LAUNCH(2);
-        case 3: GREEDY_TIMES_LAUNCH(3);
-        default: GREEDY_TIMES_LAUNCH(4);
-    }
-#undef GREEDY_TIMES_LAUNCH
-}
-
 hipError_t launch_greedy_times(int shape, const void* rec, int64_t N, uint32_t* cnt, const GreedyTimesArgs& a,
                                int64_t* base, uint8_t* leaf, int64_t P, const int64_t* now, const int64_t* unixs,
                                const uint8_t* flags, int64_t* chosen, const int64_t* ev_off, const uint32_t* ev,
                                hipStream_t st) {
     if (N <= 0 || N > kGreedyMaxNodes || P <= 0) return hipErrorInvalidValue;
+    const GreedyTreeShape ts = greedy_tree_shape(N, kGreedyTimesState);
     return with_shape(shape, [&](auto pd, auto pr) {
-        return launch_greedy_times_t<pd(), pr()>(rec, N, cnt, a, base, leaf, P, now, unixs, flags, chosen, ev_off, ev, st);
+        return with_levels(ts.nlev, [&](auto L) {
+            return launch_greedy_run<greedy_run_times<pd(), pr(), L()>>(
+                "greedy_run_times", ts.lds_bytes, st, static_cast<const NodeRec<pd(), pr()>*>(rec), N, leaf, base, cnt,
+                a, P, now, unixs, flags, chosen, ev_off, ev, (int32_t)ts.in_lds);
+        });
     });
 }
 

@@ -256,8 +256,43 @@ enum { kGreedyPrep = 1, kGreedyRun = 2, kGreedyBoth = 3 };
 hipError_t launch_greedy(int shape, const void* rec, int64_t N, uint32_t* cnt, const GreedyArgs& a, int64_t* base,
                          uint8_t* leaf, int64_t P, const uint8_t* flags, int64_t* chosen, hipStream_t st,
                          int what = kGreedyBoth);
-// dynamic LDS of the one-workgroup greedy kernels: the tree levels, with the leaves when they fit
-size_t greedy_lds_bytes(int64_t N, bool leaves_in_lds);
+// The one-workgroup run kernels' 64-ary tree over N leaf bytes (0 <= N <= kGreedyMaxNodes) beside
+// `extra` bytes of the kernel's own: the levels above the leaves, whether the leaves fit into LDS
+// with them, and the dynamic LDS size.
+struct GreedyTreeShape {
+    int nlev;
+    bool in_lds;
+    size_t lds_bytes;
+};
+inline GreedyTreeShape greedy_tree_shape(int64_t N, size_t extra) {
+    GreedyTreeShape s{0, false, extra};
+    for (int64_t sz = N; s.nlev == 0 || sz > 64; ++s.nlev) {
+        sz = (sz + 63) / 64;
+        s.lds_bytes += (size_t)((sz * 2 + 15) / 16 * 16);
+    }
+    const size_t leaves = (size_t)((N + 15) / 16 * 16);
+    s.in_lds = s.lds_bytes + leaves <= kGreedyLdsBytes;
+    if (s.in_lds) s.lds_bytes += leaves;
+    return s;
+}
+// f(L) with the level count as an integral constant (template argument: L())
+template <class F>
+inline auto with_levels(int nlev, F&& f) {
+    switch (nlev) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+// a run kernel K: one workgroup, up to kGreedyLdsBytes of dynamic LDS (allowed once per K)
+template <auto K, typename... Args>
+inline hipError_t launch_greedy_run(const char* name, size_t lds, hipStream_t st, Args... args) {
+    static const hipError_t attr =
+        hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGreedyLdsBytes);
+    if (attr != hipSuccess) return attr;
+    return klaunch(name, K, dim3(1), dim3(256), lds, st, args...);
+}
 
 // Sequential greedy at per-pod times (greedy_times.hip): pod p scored at now[p], non-decreasing.
 struct GreedyTimesArgs {
@@ -287,6 +322,13 @@ struct MergeArgs {
     int64_t win_count[kMaxWin];  // all > 0 (else the sequential kernel runs)
     int32_t win_inc[kMaxWin];    // a binding stamped now_unix falls in window w
 };
+inline MergeArgs merge_args(const GreedyArgs& g) {
+    MergeArgs m{};
+    m.n_win = g.n_win;
+    std::copy(g.win_count, g.win_count + g.n_win, m.win_count);
+    std::copy(g.win_inc, g.win_inc + g.n_win, m.win_inc);
+    return m;
+}
 // H [2][101] per-level element counts of the F (feasible) and I streams; flag != 0: use the sequential kernel
 hipError_t launch_merge_hist(const int64_t* base, const uint8_t* leaf, const uint32_t* cnt, int64_t N,
                              const MergeArgs& a, int64_t capF, int64_t capI, unsigned long long* H, int32_t* flag,

@@ -22,12 +22,13 @@ namespace crane {
 // to one is a change to all (tests/test_value_edges_gpu.py drives each with NaN, +-Inf and huge
 // inputs against the oracle):
 //  1. go_int here: the penalty int(hv * 10) of rec_hot_annotation and rec_hot_counts, i.e. of
-//     every NodeRec (K1 in kernels.hip, the streamed K1, the scatter update in update.hip).
+//     every NodeRec (K1 in kernels.hip, the streamed K1, the scatter update in update.hip), and
+//     the conversion item 3 calls.
 //  2. score_of_sum (step_node.hpp): the base int(s / wsum) with a one-instruction path for
 //     |q| < 2^31 beside the full conversion, then base - pen wrapping and the clamp.  Through
 //     score_at it is the score of the per-pair kernel and the answer tables (matrix.hip), the
 //     step path (step.hip, k1stream_body.hpp), topk.hip and select.hip.
-//  3. go_int_g and final_score (greedy_dev.hpp): base and penalty of the sequential greedy kernels
+//  3. greedy_base, pen_of_sum and final_score (greedy_dev.hpp): base and penalty of the sequential greedy kernels
 //     (greedy.hip, greedy_times.hip), the penalty recomputed from the window counts after every
 //     placement and, at per-pod times, after every count or expiry that passed.
 //  4. RunIter::next (merge.hip): base - 10 v in plain int64, no wrap — valid because M1 raises

@@ -17,6 +17,9 @@ __host__ __device__ __forceinline__ long long wide_key_of(int32_t k, int64_t g0)
     return wide_key(k >> 24, g0 + (0xFFFFFF - (k & 0xFFFFFF)));
 }
 
+// one bit per lane of the 64-lane wave
+__device__ __forceinline__ uint64_t ballot64(bool p) { return __ballot(p); }
+
 // ---- on DPP (VALU lane moves, no LDS round trip like ds_bpermute's __shfl*).  Every lane of the
 // 64-lane wave must be active (uniform control flow).
 // dpp_ctrl: quad_perm 0x00-0xFF, row_shr:k 0x110 + k, row_ror:k 0x120 + k, row_bcast:15 0x142,
@@ -33,6 +36,19 @@ __device__ __forceinline__ int32_t wave_max(int32_t v) {
     v = max(v, dpp_or<0x128>(v, v));  // row_ror:8: every lane holds its row's maximum
     return max(max(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
                max(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+// the same as a shift-and-broadcast chain ending in one readlane: row_shr 1, 2, 4, 8, then
+// row_bcast:15 / :31 carry the rows' maxima up to lane 63 (lanes without a source keep v, the
+// identity of max).  The sequential greedy kernels' form (greedy_dev.hpp): their registers and
+// their time per pod were measured with it.
+__device__ __forceinline__ int32_t wave_max_shr(int32_t v) {
+    v = max(v, dpp_or<0x111>(v, v));
+    v = max(v, dpp_or<0x112>(v, v));
+    v = max(v, dpp_or<0x114>(v, v));
+    v = max(v, dpp_or<0x118>(v, v));
+    v = max(v, dpp_or<0x142, 0xA>(v, v));
+    v = max(v, dpp_or<0x143, 0xC>(v, v));
+    return __builtin_amdgcn_readlane(v, 63);
 }
 // the same through ds_bpermute shuffles, for K3m (matrix.hip): the DPP form costs its one-node
 // instances 2 to 4 VGPRs, and the 8 x 8 ones an occupancy step

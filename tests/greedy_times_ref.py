@@ -53,6 +53,7 @@ CASES = {
     "many_events_per_pod": (None, 64, 100, 20000, 4 * NS, 71, None, False),
     "three_levels": (None, 4097, 200, 50000, NS, 74, None, False),
     "global_leaves": (None, 200000, 48, 100000, NS, 76, None, False),
+    "four_levels": (None, 262145, 48, 100000, NS, 77, None, False),
     "daemonset_mix": (None, 3000, 300, 30000, NS // 2, 75, 0.3, False),
     "odd_windows": ([(0, 1), (-60 * MIN, 2), (30 * MIN, -3)], 300, 200, 5000, 2 * NS, 72, None, False),
 }

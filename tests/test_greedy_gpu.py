@@ -36,7 +36,8 @@ def _oracle(spec, c, P, now):
 
 
 @pytest.mark.parametrize("N,P,B,seed", [(1, 5, 0, 1), (64, 200, 1000, 2), (1000, 3000, 20000, 3),
-                                        (4097, 2000, 50000, 4), (20000, 5000, 200000, 5)])
+                                        (4097, 2000, 50000, 4), (20000, 5000, 200000, 5),
+                                        (262145, 300, 100000, 6)])
 def test_greedy_vs_oracle(N, P, B, seed):
     spec = cd.default_policy_spec()
     c = synth.make_cluster(spec, N, P, n_bindings=B, seed=seed, ds_frac=0.05)
